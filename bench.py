@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the per-pixel sampling hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path over one frame of synthetic input: every pixel x every sample of the workload is
 generated, traced, shaded and accumulated on the GPU (one launch per rank), the per-rank tile shards are gathered
@@ -13,10 +13,17 @@ tile 64, seed 0x5EED.  `data/Sponza` is an empty, un-fetched submodule of the re
 the seeded procedural stand-in `minipath_amd.scenes.atrium(seed=1)` (258 432 triangles, 28-level BVH8), built by the
 reference's own builder algorithm; `config.workload` says so.  `value` is measured with the REFERENCE SEMANTICS (primary
 ray + |d.n| shading = depth 1: the reference has no bounce loop, SURVEY F2): a "ray" is one Object::intersect call, so
-rays == samples.  Secondary measurements in the same run (outside the timed region, own keys in the JSON line):
+rays == samples.  A plain run sets up, warms up, times the K steps and prints the JSON line.  With --full the same run adds
+secondary measurements (outside the timed region, own keys in the JSON line):
   "teapot_c2"    BASELINE configs[1]: teapot.obj 1920x1080 256 spp, reference semantics and the build-defined depth-8 paths
   "paths_depth8" BASELINE configs[2]: the stand-in at 1920x1080 64 spp with the build-defined max-depth-8 path extension
                  (rays = traced path segments)
+  "cpu_baseline" the CPU oracle on a bounded sample of the same frame (N = 1)
+
+--dump-outputs DIR: after the timed steps, the images the timed path returned for its last frame are written as DIR/image.npy
+(f32 RGBA, H x W x 4) and DIR/image_u8.npy (the u8 RGBA image as f32), at most 64 MB in all: an image that no longer fits whole
+is written as a fixed sample of its pixels (rows of the (H*W) x 4 view drawn with a fixed seed, ascending).  The inputs depend
+only on the arguments, so two builds' outputs compare value for value.
 
 Multi-GPU (--gpus N): one process per GPU.  Launched by torch.distributed.run (WORLD_SIZE set) the ranks run as they are;
 started as plain `python bench.py --gpus N`, the parent starts the N ranks itself (child processes, before it touches the
@@ -78,7 +85,9 @@ def parse(argv=None):
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
     ap.add_argument("--scene", default="atrium", help="'atrium' (Sponza stand-in, default), 'teapot', or a path to an .obj")
     ap.add_argument("--detail", type=float, default=1.0, help="atrium tessellation (1.0 = 258 k triangles)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the secondary measurements (teapot_c2, paths_depth8) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed frame's images to DIR/<name>.npy (f32, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--cpu-tile-stride", type=int, default=11, help="cpu_baseline renders every k-th tile")
     ap.add_argument("--cpu-threads", type=int, default=16, help="upper bound on cpu_baseline worker threads")
     ap.add_argument("--traversal", default="packets", choices=["packets", "groups"])
@@ -89,12 +98,37 @@ def parse(argv=None):
     ap.add_argument("--progressive", type=int, default=1, metavar="P",
                     help="render every frame as P progressive passes of spp/P samples (BASELINE configs[4]'s shape): the running sums "
                          "stay sharded on their GPUs, the framebuffer is gathered once per frame, after the last pass")
-    ap.add_argument("--no-extension", action="store_true", help="skip the secondary measurements (teapot_c2, paths_depth8)")
+    ap.add_argument("--no-extension", action="store_true", help="with --full: skip the secondary measurements (teapot_c2, paths_depth8)")
     ap.add_argument("--check", action="store_true", help="compare a few tiles of the GPU frame with the oracle")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.scene == "teapot":
         args.scene = TEAPOT
     return args
+
+
+DUMP_BUDGET = 64_000_000  # bytes of .npy files --dump-outputs writes at most, in all
+DUMP_SEED = 0  # fixed seed of the pixel sample of an image that no longer fits whole
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes each (name, array) of `arrays`, in order, as out_dir/<name>.npy in f32.  An array that no longer fits whole into
+    what is left of DUMP_BUDGET is written as a sample of its rows along the last axis ((H*W) x 4 for an image): as many rows as
+    fit, drawn without replacement with DUMP_SEED, in ascending order -- the same rows for the same shape on every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, a in arrays:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes + 256 > left:  # 256: upper bound of the .npy header
+            rows = a.reshape(-1, a.shape[-1])
+            k = max(0, (left - 256) // (rows.shape[1] * 4))
+            a = rows[np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=min(k, rows.shape[0]), replace=False))]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
 
 
 def spawn_ranks(n):
@@ -250,7 +284,7 @@ def main():
             frame.rebalance()  # hand the tiles the warmup frames found expensive to the waves first (same image, shorter tail)
         barrier()
         t0 = time.perf_counter()
-        img = None
+        img = img8 = None
         for _ in range(steps):
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             if args.progressive > 1:  # P passes into the resident shard, one gather + un-tile at the end of the frame
@@ -262,13 +296,15 @@ def main():
                     nxt = frame.render_pass(nxt, min(per, spp_ - nxt) if nxt + per < spp_ else 0)
                     seg_acc += frame.renderer.segments  # on the stream: no host synchronisation between the passes
                 ev[1].record()
-                out_img, _ = frame.gather_image(spp_, want_u8=True)
+                out_img, out_img8 = frame.gather_image(spp_, want_u8=True)
             else:
-                out_img, _ = frame.step(want_u8=True, kernel_events=ev)  # N > 1: the previous frame's image (pipelined gather)
+                out_img, out_img8 = frame.step(want_u8=True, kernel_events=ev)  # N > 1: the previous frame's image (pipelined gather)
             events.append(ev)
-            img = out_img if out_img is not None else img
-        last, _ = frame.flush()  # completes the last frame's gather + un-tile inside the timed region
-        img = last if last is not None else img
+            if out_img is not None:
+                img, img8 = out_img, out_img8
+        last, last8 = frame.flush()  # completes the last frame's gather + un-tile inside the timed region
+        if last is not None:
+            img, img8 = last, last8
         barrier()
         elapsed = time.perf_counter() - t0
         k_ms = sum(a.elapsed_time(b) for a, b in events) / max(len(events), 1)  # HIP events on the launch stream
@@ -282,7 +318,8 @@ def main():
             seg_total = int(segt.item())
         else:
             seg_total = seg_local
-        return {"elapsed": elapsed, "kernel_ms": k_ms, "seg_local": seg_local, "seg_total": seg_total, "img": img, "tiles": frame.all_tiles}
+        return {"elapsed": elapsed, "kernel_ms": k_ms, "seg_local": seg_local, "seg_total": seg_total, "img": img, "img8": img8,
+                "tiles": frame.all_tiles}
 
     def roofline(kernel, m, b_ray, key, cu_count):
         """SURVEY 8(d) algorithmic figure + the measured counters of the same workload (profiles/r03_counters.json), the latter
@@ -323,6 +360,9 @@ def main():
     m = measure(scene, cam, st, args.steps, args.warmup, args.balance)
     if args.depth == 0:
         assert m["seg_total"] == total_samples, (m["seg_total"], total_samples)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("image", m["img"].cpu().numpy()), ("image_u8", m["img8"].cpu().numpy())])
+
     def paths_kernel(scene_, spp_, depth_):
         """The fused path kernel the launcher picks (kernels.hip, launch_render_tiles): the pooled form for scenes whose traversal
         arrays exceed 1 MB, at least two passes of 8 samples and two segments; otherwise one pass per walk."""
@@ -350,7 +390,7 @@ def main():
         }
 
     ext = {}
-    if not args.no_extension and args.depth == 0 and args.scene == "atrium" and args.traversal == "packets":
+    if args.full and not args.no_extension and args.depth == 0 and args.scene == "atrium" and args.traversal == "packets":
         ext["paths_depth8"] = secondary(scene, cam, scene_name, scene_desc, 64, 8, steps=2, warmup=1)  # configs[2]
         tscene, tcam, tname, tdesc = make_scene(mp, ctx, TEAPOT, 1.0)
         ext["teapot_c2"] = {"depth1": secondary(tscene, tcam, tname, tdesc, 256, 0), "paths_depth8": secondary(tscene, tcam, tname, tdesc, 256, 8)}
@@ -382,7 +422,7 @@ def main():
             "roofline": roofline(kname, m, b_ray, key, cu),
         }
         out.update(ext)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, mp)
         if args.check and m["img"] is not None:
             import numpy as np

@@ -912,3 +912,31 @@ def test_bench_two_rank_progressive_rehearsal():
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 2 and d["check_mismatches"] == 0 and "3 progressive passes" in d["config"]["parallelism"]
     assert 320 * 200 * 40 < d["config"]["rays_per_step"] <= 320 * 200 * 40 * 3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_frame(tmp_path, oracle, teapot_oracle_bvh):
+    """A plain bench.py run (no --full) times exactly --steps frames, carries none of the --full keys, and --dump-outputs writes
+    the last timed frame: f32 bit-exact and u8 exact against the oracle's render of the same frame."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None); env.pop("RANK", None)
+    w, h, spp = 320, 200, 16
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--scene", "teapot",
+           "--width", str(w), "--height", str(h), "--spp", str(spp), "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["rays_per_step"] == w * h * spp
+    assert not {"teapot_c2", "paths_depth8", "cpu_baseline"} & set(d)
+    img, img8 = np.load(tmp_path / "image.npy"), np.load(tmp_path / "image_u8.npy")
+    assert img.shape == img8.shape == (h, w, 4) and img.dtype == img8.dtype == np.float32
+    of, ou8, *_ = teapot_oracle_bvh.render_image_mt(oracle.build_sampler(oracle.teapot_camera(), w, h), w, h, spp, SEED, 64, 8)
+    assert np.array_equal(bits(img), bits(of))
+    assert np.array_equal(img8, ou8.astype(np.float32))

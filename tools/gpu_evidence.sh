@@ -2,7 +2,7 @@
 # The LAST GPU action of a round: evidence from HEAD, mechanically.  Runs on the GPU box (gpurun):
 #   kernel-trace stats + PMC counter passes of the four workloads bench.py reports -> gpurun_out/cnt_*; afterwards, on the build
 #   machine:  tools/gpu_evidence.sh collect  turns them into profiles/r03_counters.json (stamped with the SHA-256 of the device
-#   sources) and copies the kernel-stats CSVs / the default bench line into profiles/r03_*.
+#   sources) and copies the kernel-stats CSVs into profiles/r03_*.  The `bench.py --full` line goes to profiles/r03_bench.json.
 set -e
 R=${GRAFT_REPO_ROOT:-$PWD}
 cd "$R"
@@ -16,7 +16,6 @@ if [ "$1" = "collect" ]; then
     cp gpurun_out/cnt_${t}_kernel_stats.csv profiles/r03_${t}_kernel_stats.csv
     cp gpurun_out/cnt_${t}.txt profiles/r03_${t}_counters.txt
   done
-  cp gpurun_out/bench_r03_final.json profiles/r03_bench.json
   tools/isa_meta.sh > profiles/r03_isa_meta.txt
   echo "profiles/r03_* written"; exit 0
 fi
@@ -24,7 +23,6 @@ bash tools/gpu_counters.sh atrium256 render_tiles_packet_kernel
 bash tools/gpu_counters.sh atrium_d8 render_paths --spp 64 --depth 8
 bash tools/gpu_counters.sh teapot256 render_tiles_packet_kernel --scene teapot
 bash tools/gpu_counters.sh teapot_d8 render_paths --scene teapot --depth 8
-collect_counters   # on the box too: the default bench line below then carries the counter-derived figures of THIS build
-python3 bench.py > gpurun_out/bench_r03_final.log 2>&1
-grep '^{' gpurun_out/bench_r03_final.log > gpurun_out/bench_r03_final.json
-cut -c1-600 gpurun_out/bench_r03_final.json
+collect_counters   # on the box too: the bench line below then carries the counter-derived figures of THIS build
+python3 bench.py --full | grep '^{' > profiles/r03_bench.json
+cut -c1-600 profiles/r03_bench.json

@@ -16,7 +16,8 @@ usage: sim_collapse.py [atrium|teapot] [detail] [n_rays]
 """
 import sys, os, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import minipath_amd as mp
 from minipath_amd import scenes
 
@@ -31,7 +32,7 @@ def fma32(a, b, c):
 
 def load(scene, detail):
     if scene == "teapot":
-        host = mp.TriangleBvh.with_obj("/root/repo/tests/golden/teapot.obj")
+        host = mp.TriangleBvh.with_obj(os.path.join(ROOT, "tests", "golden", "teapot.obj"))
     else:
         host = mp.TriangleBvh.build(*scenes.atrium(1, detail))
     i = host.info()

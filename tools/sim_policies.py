@@ -7,7 +7,8 @@ wait -- and prints VALU wave-instructions per ray for each.  Costs per phase are
 Diagnostics only (uses the oracle: test infrastructure, not product).  Results: profiles/r02_notes.md."""
 import ctypes as C, sys, os, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from oracle import pyoracle as po
 import minipath_amd as mp
 from minipath_amd import scenes

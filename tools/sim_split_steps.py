@@ -5,7 +5,8 @@ of bounce rays in the stand-in with the real child count of every visited node. 
 ray.  Diagnostics only (uses the oracle: test infrastructure)."""
 import ctypes as C, sys, os, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from oracle import pyoracle as po
 import minipath_amd as mp
 from minipath_amd import scenes

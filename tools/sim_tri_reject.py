@@ -7,10 +7,12 @@ a work unit's mask cache would hold.  numpy model (f32, fma through f64): counts
 
 usage: sim_tri_reject.py [atrium|teapot] [packets] [pixels per packet: 1|2|4]
 """
+import os
 import sys
 import numpy as np
-sys.path.insert(0, "/root/repo/tools")
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, ROOT)
 from sim_collapse import RefTree, load, build_device, slab, F, fma32
 from minipath_amd import scenes
 
