@@ -17,6 +17,7 @@
 #include <cstdlib>
 
 #include "mp_internal.h"
+#include "ray_math.h"
 
 namespace mp {
 namespace {
@@ -74,36 +75,12 @@ __device__ __forceinline__ uint32_t group_min_u(uint32_t v) {
     return v;
 }
 
-// ---- RNG: rand 0.9.3 SmallRng = Xoshiro256++ (seeded mode, include/minipath_hip.h) -----------------------------
-struct Rng {
-    uint64_t s0, s1, s2, s3;
-};
-__device__ __forceinline__ uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
-__device__ __forceinline__ uint64_t splitmix(uint64_t& state) {
-    state += 0x9e3779b97f4a7c15ull;
-    uint64_t z = state;
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ void rng_seed(Rng& r, uint64_t state) {
-    r.s0 = splitmix(state);
-    r.s1 = splitmix(state);
-    r.s2 = splitmix(state);
-    r.s3 = splitmix(state);
-}
-__device__ __forceinline__ uint32_t rng_next_u32(Rng& r) {
-    uint64_t result = rotl64(r.s0 + r.s3, 23) + r.s0;
-    uint64_t t = r.s1 << 17;
-    r.s2 ^= r.s0;
-    r.s3 ^= r.s1;
-    r.s1 ^= r.s2;
-    r.s0 ^= r.s3;
-    r.s2 ^= t;
-    r.s3 = rotl64(r.s3, 45);
-    return static_cast<uint32_t>(result >> 32);
-}
-__device__ __forceinline__ float rng_value0_1(Rng& r) { return as_f(0x3F800000u | (rng_next_u32(r) >> 9)) - 1.0f; }
+// ---- RNG: rand 0.9.3 SmallRng = Xoshiro256++ (seeded mode, include/minipath_hip.h), on 32-bit halves (ray_math.h) -------
+using rm::Rng;
+using rm::rng_seed;
+using rm::rng_value0_1;
+using rm::unit_disc;
+__device__ __forceinline__ void rng_zero(Rng& r) { r.s0 = r.s1 = r.s2 = r.s3 = rm::U64{0u, 0u}; }
 
 struct RayGen {
     mp_camera_sampler s;
@@ -116,26 +93,14 @@ struct Ray {
     float ox, oy, oz, dx, dy, dz, ix, iy, iz;
 };
 
-// geometry/mod.rs:45-54
+// geometry/mod.rs:45-54 (the short division / sqrt sequences where they are exact: ray_math.h)
 __device__ __forceinline__ void ray_new(float ox, float oy, float oz, float dx, float dy, float dz, Ray& r) {
-    float n = sqrtf(dx * dx + dy * dy + dz * dz);
     r.ox = ox; r.oy = oy; r.oz = oz;
-    r.dx = dx / n; r.dy = dy / n; r.dz = dz / n;
-    r.ix = (r.dx == 0.0f) ? INFINITY : 1.0f / r.dx;
-    r.iy = (r.dy == 0.0f) ? INFINITY : 1.0f / r.dy;
-    r.iz = (r.dz == 0.0f) ? INFINITY : 1.0f / r.dz;
+    rm::ray_dir(dx, dy, dz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
 }
 
-// rand_distr::UnitDisc: rejection on two Uniform(-1,1) draws (camera.rs:184)
-__device__ __forceinline__ void unit_disc(Rng& rng, float& x1, float& x2) {
-    for (;;) {
-        x1 = rng_value0_1(rng) * 2.0f + (-1.0f);
-        x2 = rng_value0_1(rng) * 2.0f + (-1.0f);
-        if (x1 * x1 + x2 * x2 <= 1.0f) break;
-    }
-}
-
-// CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream
+// CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream (ADVANCE = false: nothing is drawn from it afterwards)
+template <bool ADVANCE = true>
 __device__ __forceinline__ void sample_ray_rng(const RayGen& P, uint32_t x, uint32_t y, Rng& rng, Ray& r) {
     float film_u = static_cast<float>(x) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
     float film_v = static_cast<float>(y) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
@@ -144,7 +109,7 @@ __device__ __forceinline__ void sample_ray_rng(const RayGen& P, uint32_t x, uint
     float fy = P.s.film_origin_offset[1] + P.s.up[1] * fv - P.s.right[1] * fu;
     float fz = P.s.film_origin_offset[2] + P.s.up[2] * fv - P.s.right[2] * fu;
     float x1, x2;
-    unit_disc(rng, x1, x2);
+    unit_disc<ADVANCE>(rng, x1, x2);
     float a = P.s.lens_radius * x1, b = P.s.lens_radius * x2;
     float lx = P.s.right[0] * a + P.s.up[0] * b;
     float ly = P.s.right[1] * a + P.s.up[1] * b;
@@ -162,7 +127,7 @@ __device__ __forceinline__ uint64_t sample_key(const RayGen& P, uint32_t x, uint
 __device__ __forceinline__ void sample_ray(const RayGen& P, uint32_t x, uint32_t y, uint32_t sample, Ray& r) {
     Rng rng;
     rng_seed(rng, sample_key(P, x, y, sample));
-    sample_ray_rng(P, x, y, rng, r);
+    sample_ray_rng<false>(P, x, y, rng, r);
 }
 
 // ---- traversal --------------------------------------------------------------------------------------------------
@@ -1997,7 +1962,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MP_PATHS_WP
             const uint32_t s = s0 + static_cast<uint32_t>(sub);
             const bool act = inpix && s >= s_begin && s < s_end;
             Rng rng;
-            rng.s0 = rng.s1 = rng.s2 = rng.s3 = 0;
+            rng_zero(rng);
             Ray r;
             r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
             {
@@ -2109,10 +2074,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MP_POOL_WPE
     auto park_store = [&](int j, const Rng& rng, float L, float thr, uint32_t flags) {
         // streamed (non-temporal): 200 MB of parked state per launch must not push the scene out of the L2
         uint32_t* p = park + j * 64 + lane;
-        __builtin_nontemporal_store(static_cast<uint32_t>(rng.s0), p + 0 * QN); __builtin_nontemporal_store(static_cast<uint32_t>(rng.s0 >> 32), p + 1 * QN);
-        __builtin_nontemporal_store(static_cast<uint32_t>(rng.s1), p + 2 * QN); __builtin_nontemporal_store(static_cast<uint32_t>(rng.s1 >> 32), p + 3 * QN);
-        __builtin_nontemporal_store(static_cast<uint32_t>(rng.s2), p + 4 * QN); __builtin_nontemporal_store(static_cast<uint32_t>(rng.s2 >> 32), p + 5 * QN);
-        __builtin_nontemporal_store(static_cast<uint32_t>(rng.s3), p + 6 * QN); __builtin_nontemporal_store(static_cast<uint32_t>(rng.s3 >> 32), p + 7 * QN);
+        __builtin_nontemporal_store(rng.s0.lo, p + 0 * QN); __builtin_nontemporal_store(rng.s0.hi, p + 1 * QN);
+        __builtin_nontemporal_store(rng.s1.lo, p + 2 * QN); __builtin_nontemporal_store(rng.s1.hi, p + 3 * QN);
+        __builtin_nontemporal_store(rng.s2.lo, p + 4 * QN); __builtin_nontemporal_store(rng.s2.hi, p + 5 * QN);
+        __builtin_nontemporal_store(rng.s3.lo, p + 6 * QN); __builtin_nontemporal_store(rng.s3.hi, p + 7 * QN);
         __builtin_nontemporal_store(as_u(L), p + 8 * QN); __builtin_nontemporal_store(as_u(thr), p + 9 * QN); __builtin_nontemporal_store(flags, p + 10 * QN);
     };
     // bounce ray of a path that is still alive: into the queue (compacted over the lanes whose ray can reach the scene at all)
@@ -2155,7 +2120,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MP_POOL_WPE
                 const uint32_t s = s0 + static_cast<uint32_t>(j * S + sub);
                 const bool act = inpix && s >= s_begin && s < s_end;
                 Rng rng;
-                rng.s0 = rng.s1 = rng.s2 = rng.s3 = 0;
+                rng_zero(rng);
                 Ray r;
                 r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
                 {
@@ -2206,8 +2171,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MP_POOL_WPE
                     if (__ballot(alive) == 0) continue;  // the whole pass is finished: its parked L / flags stay as they are
                     Rng rng;
                     auto ld = [&](int row) { return static_cast<uint64_t>(__builtin_nontemporal_load(p + row * QN)); };
-                    rng.s0 = ld(0) | (ld(1) << 32); rng.s1 = ld(2) | (ld(3) << 32);
-                    rng.s2 = ld(4) | (ld(5) << 32); rng.s3 = ld(6) | (ld(7) << 32);
+                    auto ld2 = [&](int row) { return rm::U64{__builtin_nontemporal_load(p + row * QN), __builtin_nontemporal_load(p + (row + 1) * QN)}; };
+                    rng.s0 = ld2(0); rng.s1 = ld2(2);
+                    rng.s2 = ld2(4); rng.s3 = ld2(6);
                     float L[1] = {as_f(static_cast<uint32_t>(ld(8)))}, thr[1] = {as_f(static_cast<uint32_t>(ld(9)))};
                     bool primary_hit = (flags & kPoolPrimary) != 0u;
                     Ray r;
@@ -2339,7 +2305,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
             const bool slot = inpix && sl < P.sc;       // a path slot of the batch exists for this lane
             const bool act = slot && s < P.s_end;       // ... and holds a sample of this launch
             Rng rng;
-            rng.s0 = rng.s1 = rng.s2 = rng.s3 = 0;
+            rng_zero(rng);
             Ray r;
             r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
             if (act) {
@@ -2375,8 +2341,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8))) voi
                 const uint32_t p = pbase + sl;
                 P.st.flags[p] = act ? (kWfAlive | kWfValid) : 0u;
                 if (act) {
-                    P.st.rng[0 * static_cast<size_t>(n) + p] = rng.s0; P.st.rng[1 * static_cast<size_t>(n) + p] = rng.s1;
-                    P.st.rng[2 * static_cast<size_t>(n) + p] = rng.s2; P.st.rng[3 * static_cast<size_t>(n) + p] = rng.s3;
+                    P.st.rng[0 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s0); P.st.rng[1 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s1);
+                    P.st.rng[2 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s2); P.st.rng[3 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s3);
                     P.st.ray[0 * static_cast<size_t>(n) + p] = r.ox; P.st.ray[1 * static_cast<size_t>(n) + p] = r.oy;
                     P.st.ray[2 * static_cast<size_t>(n) + p] = r.oz; P.st.ray[3 * static_cast<size_t>(n) + p] = r.dx;
                     P.st.ray[4 * static_cast<size_t>(n) + p] = r.dy; P.st.ray[5 * static_cast<size_t>(n) + p] = r.dz;
@@ -2401,8 +2367,8 @@ __global__ __launch_bounds__(256) void wf_vertex_kernel(WfParams P) {
         uint32_t fl = P.st.flags[p];
         if (!(fl & kWfAlive)) continue;
         Rng rng;
-        rng.s0 = P.st.rng[0 * static_cast<size_t>(n) + p]; rng.s1 = P.st.rng[1 * static_cast<size_t>(n) + p];
-        rng.s2 = P.st.rng[2 * static_cast<size_t>(n) + p]; rng.s3 = P.st.rng[3 * static_cast<size_t>(n) + p];
+        rng.s0 = rm::u64_split(P.st.rng[0 * static_cast<size_t>(n) + p]); rng.s1 = rm::u64_split(P.st.rng[1 * static_cast<size_t>(n) + p]);
+        rng.s2 = rm::u64_split(P.st.rng[2 * static_cast<size_t>(n) + p]); rng.s3 = rm::u64_split(P.st.rng[3 * static_cast<size_t>(n) + p]);
         Ray r;
         r.ox = P.st.ray[0 * static_cast<size_t>(n) + p]; r.oy = P.st.ray[1 * static_cast<size_t>(n) + p];
         r.oz = P.st.ray[2 * static_cast<size_t>(n) + p]; r.dx = P.st.ray[3 * static_cast<size_t>(n) + p];
@@ -2420,8 +2386,8 @@ __global__ __launch_bounds__(256) void wf_vertex_kernel(WfParams P) {
 #pragma unroll
         for (int c = 0; c < N; c++) { P.st.L[c * static_cast<size_t>(n) + p] = L[c]; P.st.thr[c * static_cast<size_t>(n) + p] = thr[c]; }
         if (alive) {
-            P.st.rng[0 * static_cast<size_t>(n) + p] = rng.s0; P.st.rng[1 * static_cast<size_t>(n) + p] = rng.s1;
-            P.st.rng[2 * static_cast<size_t>(n) + p] = rng.s2; P.st.rng[3 * static_cast<size_t>(n) + p] = rng.s3;
+            P.st.rng[0 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s0); P.st.rng[1 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s1);
+            P.st.rng[2 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s2); P.st.rng[3 * static_cast<size_t>(n) + p] = rm::u64_join(rng.s3);
             P.st.ray[0 * static_cast<size_t>(n) + p] = r.ox; P.st.ray[1 * static_cast<size_t>(n) + p] = r.oy;
             P.st.ray[2 * static_cast<size_t>(n) + p] = r.oz; P.st.ray[3 * static_cast<size_t>(n) + p] = r.dx;
             P.st.ray[4 * static_cast<size_t>(n) + p] = r.dy; P.st.ray[5 * static_cast<size_t>(n) + p] = r.dz;
