@@ -301,6 +301,41 @@ int mp_scene_device_tree(const mp_scene *scene, int which, float *nodes, uint32_
 int mp_trace_rays(mp_ctx *ctx, const mp_scene *scene, const float *d_ox, const float *d_oy, const float *d_oz,
                   const float *d_dx, const float *d_dy, const float *d_dz, uint64_t n, const mp_hits_soa *hits,
                   void *stream);
+
+/* ---- Bounded and occlusion queries (build-defined; no reference counterpart) ------------------------------------
+ * The rays are those of mp_trace_rays (Ray::new(o, d) on the device); d_tmax (nullable) holds one f32 bound per ray.
+ *   Effective bound  b = min(tmax, FLT_MAX); d_tmax == NULL means b = FLT_MAX for every ray.  A ray with NaN or tmax <= 0 is a
+ *                    miss and is not occluded (it is not walked).
+ *   Bounded hit      W(b) = TriangleBvh::intersect (ray_bvh_intersection.rs:26-96) with best.t initialised to b instead of
+ *                    FloatType::MAX (:34-37); nothing else changes: the slab limit node.intersect(ray, box, best.t), the pop
+ *                    test node_t1 > best.t (:40-44), the leaf test t <= max_t (:125) and the strict hit.t < best.t (:59).  A
+ *                    hit is therefore reported only when t < b.  Sphere scenes and members: primitives.rs:16-48 gives t and
+ *                    t < b.  Object groups and instances: every member is walked with best.t = b; members combine as in
+ *                    mp_trace_rays (strict <, in member order), so every mp_hits_soa field, d_instance included, keeps its
+ *                    meaning; a miss writes mp_trace_rays' miss record (t = FLT_MAX, prim = MP_NO_PRIM, zeros).
+ *   Occluded         = W(b) reports a hit.  The any-hit walk stops at the first packet in which a triangle passes the leaf
+ *                    test with t < b.  Before its first hit W(b) has best.t == b, so it pushes, culls and tests exactly as the
+ *                    any-hit walk does: both accept their first hit in the same leaf, or neither ever does.  occluded ==
+ *                    (bounded prim != MP_NO_PRIM) holds EXACTLY, for every ray and every tmax, boundary values included.  Which
+ *                    triangle stopped the walk is not part of the result.
+ * Consequences (t* = mp_trace_rays' distance; the arguments are in minipath_amd/csrc/kernels.hip above query_rays_kernel):
+ *   1. d_tmax == NULL or tmax >= FLT_MAX: the same bits as mp_trace_rays in every mp_hits_soa field.
+ *   2. The unbounded query misses, or t* >= b: the bounded query misses.
+ *   3. The bounded query hits at t: t < b, and t* <= t unless the ray crosses two boxes of the band described in 4.
+ *   4. b at least the slab entry t1 of every box the ray enters (e.g. b >= the slab exit of the scene's box plus a margin for
+ *      child boxes rounded outward): the result is exactly (t* < b ? mp_trace_rays' record : miss).  Below that, a box whose
+ *      floating-point entry lies beyond the distance of a triangle it holds (grazing rays, walls on box faces) can make the
+ *      bounded hit differ from the unbounded one although t* < b -- as the reference's own walk does with any best.t.
+ *   5. The wide and the literal device trees give the same result for bounded walks (minipath_amd/csrc/device_tree.cpp).
+ * There is no tmin: hits with t >= 0 count (as in the reference's own test); callers offset the origin, as the path extension
+ * does (1e-4 along the normal).
+ * Argument checks as mp_trace_rays; n == 0 is a no-op.  d_occluded: n bytes, 1 = occluded, 0 = not. */
+int mp_trace_rays_bounded(mp_ctx *ctx, const mp_scene *scene, const float *d_ox, const float *d_oy, const float *d_oz,
+                          const float *d_dx, const float *d_dy, const float *d_dz, const float *d_tmax /* nullable */,
+                          uint64_t n, const mp_hits_soa *hits, void *stream);
+int mp_occluded_rays(mp_ctx *ctx, const mp_scene *scene, const float *d_ox, const float *d_oy, const float *d_oz,
+                     const float *d_dx, const float *d_dy, const float *d_dz, const float *d_tmax /* nullable */,
+                     uint64_t n, uint8_t *d_occluded /* 0 / 1 */, void *stream);
 /* CameraSampler::sample_ray (camera.rs:176-191) batched, seeded mode: writes unit-direction rays for sample s of
  * every pixel of `block` (x fastest) -- the ray stream of the staged (wavefront) pipeline. */
 int mp_generate_rays(mp_ctx *ctx, const mp_camera_sampler *sampler, const mp_settings *settings, mp_block block,

@@ -212,6 +212,8 @@ SIGNATURES = {
     "mp_scene_export": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mp_scene_device_tree": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mp_trace_rays": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint64, C.POINTER(HitsSoA), C.c_void_p]),
+    "mp_trace_rays_bounded": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 7 + [C.c_uint64, C.POINTER(HitsSoA), C.c_void_p]),
+    "mp_occluded_rays": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_void_p] * 7 + [C.c_uint64, C.c_void_p, C.c_void_p]),
     "mp_generate_rays": (
         C.c_int,
         [C.c_void_p, C.POINTER(SamplerStruct), C.POINTER(SettingsStruct), Block, C.c_uint32] + [C.c_void_p] * 6 + [C.c_void_p],

@@ -22,6 +22,8 @@
 //   popped in descending order in both trees and p's children take p's place in N's list, so the leaves are reached in the same
 //   order with the same best.t.  A node is absorbed only if ALL its child boxes are FP-nested in its own box; the check is on
 //   the very floats the kernels read.
+//   The argument uses only that best.t never grows, not its starting value: it holds for the bounded and any-hit walks of
+//   mp_trace_rays_bounded / mp_occluded_rays (best.t starting at the ray's bound) as well.
 //   With an infinite inverse component the argument fails for one degenerate case (inv = -inf from a negative denormal
 //   direction, a flat box exactly at the origin coordinate), so those rays -- rare -- walk the literal tree.
 #include <algorithm>

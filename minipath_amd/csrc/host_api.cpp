@@ -1012,6 +1012,42 @@ int mp_trace_rays(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, const f
     });
 }
 
+// the checks of mp_trace_rays; exactly one of hits / d_occluded is used
+static int query_rays(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, const float* d_oy, const float* d_oz,
+                      const float* d_dx, const float* d_dy, const float* d_dz, const float* d_tmax, uint64_t n,
+                      const mp_hits_soa* hits, uint8_t* d_occluded, void* stream) {
+    DeviceGuard g(ctx->device);
+    std::string err;
+    const uint32_t bpc = ctx->blocks_per_cu.load();
+    int rc = launch_query_rays(scene->dev, d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax, n, hits, d_occluded,
+                               ctx->cu_count * (bpc ? static_cast<int>(bpc) : 8) / 8, stream, err);
+    if (rc) return fail(rc, err);
+    return MP_OK;
+}
+
+int mp_trace_rays_bounded(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, const float* d_oy, const float* d_oz,
+                          const float* d_dx, const float* d_dy, const float* d_dz, const float* d_tmax, uint64_t n,
+                          const mp_hits_soa* hits, void* stream) {
+    return guarded([&]() -> int {
+    if (!ctx || !scene || !hits) return fail(MP_ERR_INVALID, "NULL argument");
+    if (n && (!d_ox || !d_oy || !d_oz || !d_dx || !d_dy || !d_dz)) return fail(MP_ERR_INVALID, "NULL ray array");
+    if (scene->ctx != ctx) return fail(MP_ERR_INVALID, "scene belongs to another context");
+    return query_rays(ctx, scene, d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax, n, hits, nullptr, stream);
+    });
+}
+
+int mp_occluded_rays(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, const float* d_oy, const float* d_oz,
+                     const float* d_dx, const float* d_dy, const float* d_dz, const float* d_tmax, uint64_t n,
+                     uint8_t* d_occluded, void* stream) {
+    return guarded([&]() -> int {
+    if (!ctx || !scene) return fail(MP_ERR_INVALID, "NULL argument");
+    if (n && (!d_ox || !d_oy || !d_oz || !d_dx || !d_dy || !d_dz)) return fail(MP_ERR_INVALID, "NULL ray array");
+    if (n && !d_occluded) return fail(MP_ERR_INVALID, "NULL output array");
+    if (scene->ctx != ctx) return fail(MP_ERR_INVALID, "scene belongs to another context");
+    return query_rays(ctx, scene, d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax, n, nullptr, d_occluded, stream);
+    });
+}
+
 int mp_generate_rays(mp_ctx* ctx, const mp_camera_sampler* sampler, const mp_settings* settings, mp_block block,
                      uint32_t sample, float* d_ox, float* d_oy, float* d_oz, float* d_dx, float* d_dy, float* d_dz,
                      void* stream) {

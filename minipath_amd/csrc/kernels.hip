@@ -154,9 +154,17 @@ __device__ __forceinline__ uint64_t mask_ge(float a, float b) { return __builtin
 // QS = queue stride = ray slots.  QS == 64: the wave's LDS queue (rows ox,oy,oz,dx,dy,dz; the hit aliases rows 0..3; inverse
 // directions computed here, one slot per lane).  QS > 64: the pooled path kernel's queue in global memory (rows 0..5 origin and
 // direction, 6..8 inverse direction as Ray::new has it, 9..12 the hit: the rays are needed again for shading).
-template <bool PATCH_NAN, bool BFE, int QS = 64>
+// MODE (ray queries, include/minipath_hip.h "Bounded and occlusion queries"; QS == 64 only): kClosest = the walk above, best.t
+// starts at f32::MAX; kBounded = the same walk with best.t -- and every lane's candidate tl -- starting at the ray's bound b
+// (`pb` = b of queue slot `lane`, fetched by the group that pulls the slot, like the inverse direction); kAnyHit = that walk
+// ended at the first packet in which a lane accepts a triangle (t < b): row 1 of the slot then holds only prim = 0 (occluded)
+// or MP_NO_PRIM.  Before its first hit the bounded walk's best.t is b, so both walks push, cull and test exactly alike up to
+// that packet: occluded == (the bounded walk hits), for every ray and bound.
+enum { kClosest = 0, kBounded = 1, kAnyHit = 2 };
+template <bool PATCH_NAN, bool BFE, int QS = 64, int MODE = kClosest>
 __device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base,
-                                                int nrays) {
+                                                int nrays, float pb = FLT_MAX) {
+    static_assert(MODE == kClosest || QS == 64, "ray queries run on the wave's LDS queue");
     constexpr int HB = QS == 64 ? 0 : 9;  // first hit row
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const int g = lane >> 3, li = lane & 7;
@@ -189,7 +197,11 @@ __device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __res
         //    order, ascending lane) and replaces on strict `<` (:118-136, :59): the winner is the earliest candidate
         //    that attains the minimum t.  Every lane kept its own earliest minimum; ties across lanes go to the
         //    smaller (visit sequence, lane).
-        if (slot >= 0 && sp == 0 && pk == pk_end) {
+        if (MODE == kAnyHit && slot >= 0 && sp == 0 && pk == pk_end) {
+            if (li == 0) q[1 * 64 + slot] = as_f(pkl);  // 0 = occluded (set where the walk stopped), MP_NO_PRIM = not
+            slot = -1;
+        }
+        if (MODE != kAnyHit && slot >= 0 && sp == 0 && pk == pk_end) {
             float tmin = group_min_t(tl);
             uint32_t key = (pkl != kNoPrim && tl == tmin) ? ((seql << 3) | static_cast<uint32_t>(li)) : 0xFFFFFFFFu;
             uint32_t kmin = group_min_u(key);
@@ -219,15 +231,16 @@ __device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __res
             int mine = head + __popcll(gm & groups_below);
             head += __popcll(gm);
             // (ds_bpermute reads the source lane's register whether or not that lane is enabled; an out-of-range `mine` wraps)
-            float fix = 0.0f, fiy = 0.0f, fiz = 0.0f;
+            float fix = 0.0f, fiy = 0.0f, fiz = 0.0f, fb = FLT_MAX;
             if (QS == 64) { fix = __shfl(pix, mine & 63); fiy = __shfl(piy, mine & 63); fiz = __shfl(piz, mine & 63); }
+            if (MODE != kClosest) fb = __shfl(pb, mine & 63);
             if (slot < 0 && mine < nrays) {
                 slot = mine;
                 ox = q[0 * QS + mine]; oy = q[1 * QS + mine]; oz = q[2 * QS + mine];
                 dx = q[3 * QS + mine]; dy = q[4 * QS + mine]; dz = q[5 * QS + mine];
                 if (QS != 64) { fix = q[6 * QS + mine]; fiy = q[7 * QS + mine]; fiz = q[8 * QS + mine]; }
                 ix = fix; iy = fiy; iz = fiz;
-                best_t = FLT_MAX; tl = FLT_MAX; ul = 0; vl = 0; pkl = kNoPrim; seql = 0; seq = 0;
+                best_t = fb; tl = fb; ul = 0; vl = 0; pkl = kNoPrim; seql = 0; seq = 0;  // :34-37, best.t = b
                 pk = pk_end = 0;
                 sp = 1;
                 if (li == 0) stack[0] = make_uint2(root, as_u(-INFINITY));  // :28-32
@@ -292,6 +305,13 @@ __device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __res
             float v = inv_det * fma_dot(dx, dy, dz, qx, qy, qz);
             float t = inv_det * fma_dot(e2x, e2y, e2z, qx, qy, qz);
             bool valid = (u >= 0.0f) & (v >= 0.0f) & ((u + v) <= 1.0f) & (t >= 0.0f) & (t <= best_t);  // :125
+            if (MODE == kAnyHit) {
+                // tl == best_t == b for the whole walk: a set bit in the group's byte of the ballot is :59's `hit.t < best.t` for
+                // some triangle of this packet.  The ray is done: empty stack, no pending packet, the group pulls the next ray.
+                if ((__ballot(valid && t < tl) >> (g * 8)) & 0xFFull) { sp = 0; pk = pk_end; pkl = 0u; }
+                else pk++;
+                continue;
+            }
             if (valid && t < tl) { tl = t; ul = u; vl = v; pkl = pk; seql = seq; }
             seq++;
             pk++;
@@ -304,14 +324,15 @@ __device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __res
 // A queue without a ray that has an infinite inverse direction component (a zero -- or, denormals being kept, a tiny --
 // direction component: geometry/mod.rs:49-53) cannot produce 0 * inf in the slab test: it runs the variant without the NaN
 // patches (six VALU per node step less) on the wide tree.  Wave-uniform choice per call.
-template <bool BFE = false>
-__device__ __forceinline__ void trace_wave(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base, int nrays) {
+template <bool BFE = false, int MODE = kClosest>
+__device__ __forceinline__ void trace_wave(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base, int nrays,
+                                           float pb = FLT_MAX) {
     const int lane = static_cast<int>(threadIdx.x) & 63;
     const float qx = q[3 * 64 + lane], qy = q[4 * 64 + lane], qz = q[5 * 64 + lane];
     const float ix = (qx == 0.0f) ? INFINITY : 1.0f / qx, iy = (qy == 0.0f) ? INFINITY : 1.0f / qy, iz = (qz == 0.0f) ? INFINITY : 1.0f / qz;
     const bool inf = lane < nrays && (fabsf(ix) == INFINITY || fabsf(iy) == INFINITY || fabsf(iz) == INFINITY);
-    if (__ballot(inf) != 0) trace_wave_impl<true, BFE>(sc, q, stack_base, nrays);
-    else trace_wave_impl<false, BFE>(sc, q, stack_base, nrays);
+    if (__ballot(inf) != 0) trace_wave_impl<true, BFE, 64, MODE>(sc, q, stack_base, nrays, pb);
+    else trace_wave_impl<false, BFE, 64, MODE>(sc, q, stack_base, nrays, pb);
 }
 
 // ... and for the pooled path kernel's queue of QS > 64 slots in global memory (inverse directions in rows 6..8)
@@ -434,43 +455,59 @@ struct GroupHit {
 // Closest hit of the wave's rays (one per lane, `act` = lane holds a ray) with the group walk: compaction of the lanes whose ray
 // can reach the object into the wave's ray queue, trace_wave, results back to the lanes.  OBJ: once per member of the object
 // group, in order, closest wins with a strict `<` (the first member keeps ties).
-template <bool OBJ, bool BFE = false>
+// MODE != kClosest (ray queries): `b` = this lane's bound (> 0, finite; include/minipath_hip.h).  Every member is walked with
+// best.t = b and h.t starts at b, so a member's hit counts only below b and the combination is today's; h.t = f32::MAX again
+// for a miss.  kAnyHit: a lane whose ray is occluded is not queued for later members; h.prim = 0 marks it.
+template <bool OBJ, bool BFE = false, int MODE = kClosest>
 __device__ __forceinline__ void trace_objects(const DevScene& sc, const Ray& r, bool act, float* __restrict__ q,
-                                              uint2* __restrict__ stack, GroupHit& h) {
-    h.t = FLT_MAX; h.u = h.v = 0.0f; h.prim = kNoPrim; h.inst = 0u;
+                                              uint2* __restrict__ stack, GroupHit& h, float b = FLT_MAX) {
+    h.t = MODE == kClosest ? FLT_MAX : b; h.u = h.v = 0.0f; h.prim = kNoPrim; h.inst = 0u;
     auto pass = [&](const DevScene& sk, const Ray& rk, uint32_t k) {
+        const bool open = act && (MODE != kAnyHit || h.prim == kNoPrim);
         if (OBJ && sk.kind == 1u) {  // a Sphere member (scene/primitives.rs:16-48): lane-parallel, no walk; prim 0
             float ts, nn[3];
-            if (act && sphere_intersect(sk, rk, ts, nn) && ts < h.t) { h.t = ts; h.prim = 0u; h.u = h.v = 0.0f; h.inst = k; }
+            if (open && sphere_intersect(sk, rk, ts, nn) && ts < h.t) { h.t = ts; h.prim = 0u; h.u = h.v = 0.0f; h.inst = k; }
             return;
         }
-        const bool queued = act && may_hit_scene(sk, rk);
+        const bool queued = open && may_hit_scene(sk, rk);
         const uint64_t am = __ballot(queued);
         const int n = __popcll(am), rank = rank_below(am);
         if (queued) {
             q[0 * 64 + rank] = rk.ox; q[1 * 64 + rank] = rk.oy; q[2 * 64 + rank] = rk.oz;
             q[3 * 64 + rank] = rk.dx; q[4 * 64 + rank] = rk.dy; q[5 * 64 + rank] = rk.dz;
         }
+        float pb = FLT_MAX;
+        if (MODE != kClosest) {
+            // the bound of queue slot `lane` into lane `lane` (ds_permute = scatter): queued lanes send to their rank, the others to
+            // the slots above n, so that every lane has exactly one sender
+            const int dst = queued ? rank : n + (static_cast<int>(threadIdx.x & 63) - rank);
+            pb = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(b)));
+        }
         wave_lds_sync();
-        trace_wave<BFE>(sk, q, stack, n);
+        trace_wave<BFE, MODE>(sk, q, stack, n, pb);
         if (queued) {
             const uint32_t prim = as_u(q[1 * 64 + rank]);
-            const float t = q[0 * 64 + rank];
-            if (prim != kNoPrim && t < h.t) { h.t = t; h.prim = prim; h.u = q[2 * 64 + rank]; h.v = q[3 * 64 + rank]; h.inst = k; }
+            if (MODE == kAnyHit) {
+                if (prim != kNoPrim) { h.prim = 0u; h.inst = k; }
+            } else {
+                const float t = q[0 * 64 + rank];
+                if (prim != kNoPrim && t < h.t) { h.t = t; h.prim = prim; h.u = q[2 * 64 + rank]; h.v = q[3 * 64 + rank]; h.inst = k; }
+            }
         }
         wave_lds_sync();
     };
     if (!OBJ) {
         pass(sc, r, 0u);
-        return;
+    } else {
+        for (uint32_t k = 0; k < sc.inst_count; k++) {
+            DevScene sk;
+            Ray rk;
+            object_scene(sc, k, sk);
+            object_ray(sc, k, r, rk);
+            pass(sk, rk, k);
+        }
     }
-    for (uint32_t k = 0; k < sc.inst_count; k++) {
-        DevScene sk;
-        Ray rk;
-        object_scene(sc, k, sk);
-        object_ray(sc, k, r, rk);
-        pass(sk, rk, k);
-    }
+    if (MODE != kClosest && h.prim == kNoPrim) h.t = FLT_MAX;
 }
 
 // Normal and material id of a hit on member `inst` of an object group (r = the world ray).  A Sphere member's normal is that of
@@ -2542,6 +2579,62 @@ struct TraceParams {
     uint32_t lds_per_wave;
 };
 
+// The stores of trace_rays_kernel's HitRecord, for query_rays_kernel.  (trace_rays_kernel keeps its own inline copy: calling these
+// changes its scalar register allocation, and its code stays as measured.)
+// HitRecord of a Sphere scene for ray i (primitives.rs:40-46): {t, point, normal, material 0, texture_coords origin}; a miss
+// writes t = f32::MAX, MP_NO_PRIM and zeros
+__device__ __forceinline__ void store_sphere_hit(const TraceParams& P, uint64_t i, const Ray& r, bool hit, float t, const float nn[3]) {
+    if (P.hits.d_t) P.hits.d_t[i] = t;
+    if (P.hits.d_prim) P.hits.d_prim[i] = hit ? 0u : kNoPrim;
+    if (P.hits.d_u) P.hits.d_u[i] = 0.0f;
+    if (P.hits.d_v) P.hits.d_v[i] = 0.0f;
+    for (int k = 0; k < 3; k++) {
+        const float o = k == 0 ? r.ox : k == 1 ? r.oy : r.oz, d = k == 0 ? r.dx : k == 1 ? r.dy : r.dz;
+        if (P.hits.d_point) P.hits.d_point[i * 3 + k] = hit ? o + d * t : 0.0f;
+        if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = hit ? nn[k] : 0.0f;
+        if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = 0.0f;
+    }
+    if (P.hits.d_material) P.hits.d_material[i] = 0u;
+    if (P.hits.d_instance) P.hits.d_instance[i] = 0u;
+}
+
+// HitRecord of ray i from the group walk's closest hit (ray_bvh_intersection.rs:66-95); a miss writes zeros beyond t / prim
+template <bool OBJ>
+__device__ __forceinline__ void store_group_hit(const TraceParams& P, uint64_t i, const GroupHit& gh) {
+    const float t = gh.t, u = gh.u, v = gh.v;
+    const uint32_t prim = gh.prim, inst = gh.inst;
+    if (P.hits.d_t) P.hits.d_t[i] = t;
+    if (P.hits.d_prim) P.hits.d_prim[i] = prim;
+    if (P.hits.d_u) P.hits.d_u[i] = u;
+    if (P.hits.d_v) P.hits.d_v[i] = v;
+    if (P.hits.d_point || P.hits.d_normal || P.hits.d_tex || P.hits.d_material) {
+        float pt[3] = {0, 0, 0}, nn[3] = {0, 0, 0}, tx[3] = {0, 0, 0};
+        uint32_t mat = 0;  // HitRecord.material (geometry/mod.rs:78)
+        if (prim != kNoPrim) {
+            Ray r;  // rebuilt here so that no ray registers stay live across the walk
+            ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r);
+            DevScene so = P.scene;  // the member the ray hit (its normals, texture coordinates, material ids)
+            if (OBJ) object_scene(P.scene, inst, so);
+            mat = OBJ ? object_normal(P.scene, inst, r, prim, u, v, nn) : resolve_normal(so, prim, u, v, nn);
+            pt[0] = r.ox + r.dx * t; pt[1] = r.oy + r.dy * t; pt[2] = r.oz + r.dz * t;  // geometry/mod.rs:56-58
+            if (!OBJ || so.kind == 0u) {  // a Sphere member's texture_coords are the origin (primitives.rs:45)
+                const uint32_t* vi = so.vidx + static_cast<size_t>(prim) * 3;
+                const float *t0 = so.vtex + 3 * static_cast<size_t>(vi[0]), *t1 = so.vtex + 3 * static_cast<size_t>(vi[1]),
+                            *t2 = so.vtex + 3 * static_cast<size_t>(vi[2]);
+                float w = 1.0f - u - v;
+                for (int k = 0; k < 3; k++) tx[k] = t0[k] * w + t1[k] * u + t2[k] * v;
+            }
+        }
+        for (int k = 0; k < 3; k++) {
+            if (P.hits.d_point) P.hits.d_point[i * 3 + k] = pt[k];
+            if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = nn[k];
+            if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = tx[k];
+        }
+        if (P.hits.d_material) P.hits.d_material[i] = mat;
+    }
+    if (P.hits.d_instance) P.hits.d_instance[i] = inst;
+}
+
 template <bool OBJ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void trace_rays_kernel(TraceParams) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -2616,6 +2709,82 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 if (P.hits.d_material) P.hits.d_material[i] = mat;
             }
             if (P.hits.d_instance) P.hits.d_instance[i] = inst;
+        }
+    }
+}
+
+// ---- bounded closest hit and occlusion over SoA ray streams (include/minipath_hip.h "Bounded and occlusion queries") ----------
+// trace_rays_kernel with a per-ray bound b = min(tmax, f32::MAX) (d_tmax NULL: f32::MAX): MODE = kBounded writes the HitRecord of
+// the walk with best.t = b (same fields, same miss record as mp_trace_rays), kAnyHit one byte per ray: 1 = that walk hits.
+// A ray with NaN or non-positive tmax is a miss and is not walked.  Same grid, LDS and 8-waves-per-SIMD rules as trace_rays_kernel.
+//
+// Why the facts of include/minipath_hip.h hold (t* = the unbounded walk's distance, W(b) = the walk with best.t starting at b):
+//  1. b = f32::MAX is the unbounded walk's own start: every push, cull, leaf test and acceptance is the same, so are the bits
+//     written (the miss record included: tl = FLT_MAX, no candidate, u = v = 0, t = FLT_MAX).
+//  2. The unbounded walk's best.t starts at f32::MAX >= b and never drops below t* >= b until it ends; W(b)'s never exceeds b.
+//     Every slab limit and pop test of W(b) is therefore at least as strict, so W(b) visits a subset of the unbounded walk's
+//     leaves, in the same relative order (children are pushed in ascending, popped in descending slot order in both).  A
+//     triangle W(b) could accept has t < b <= t* and passes the leaf test in a leaf the unbounded walk visits with best.t >=
+//     t* > t, which would have made its result < t*: there is none, W(b) misses.
+//  3. W(b) accepts only t < b.  While W(b)'s best.t <= the unbounded walk's (true at the start), every box W(b) pushes and pops
+//     the unbounded walk pushes and pops too, and every leaf both visit leaves W(b)'s best.t <= the unbounded walk's; so W(b)'s
+//     result is >= t* unless the unbounded walk accepts a triangle in a leaf that W(b) culled.  That needs a triangle whose
+//     distance lies below its box's floating-point entry (the band of 4), and W(b) then has to accept, in another such box,
+//     a triangle below t*: two band boxes on one ray.  Outside that, t* <= t.
+//  4. If b is at least the slab entry t1 of every box the ray enters, the bound b in t2 = min(exit, best.t) and in the pop
+//     test removes no box that f32::MAX would keep before the first hit; from the first hit on both walks carry the same
+//     best.t (the same leaves were visited with the same candidates).  So W(b) == the unbounded walk when t* < b, and a miss
+//     otherwise (fact 2).
+//  5. The wide tree's argument (device_tree.cpp) uses only that best.t never grows: it holds for any starting value.
+// Occluded == (W(b) hits): the any-hit walk is W(b) up to its first accepting packet (best.t == b in both until then).
+struct QueryParams {
+    TraceParams tr;
+    const float* tmax;
+    uint8_t* occluded;
+};
+
+template <bool OBJ, int MODE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void query_rays_kernel(QueryParams) {
+    static_assert(MODE == kBounded || MODE == kAnyHit, "a query mode");
+    extern __shared__ __align__(16) unsigned char smem[];
+    typedef const __attribute__((address_space(4))) QueryParams* kquery_t;
+    kquery_t KP = (kquery_t)__builtin_amdgcn_kernarg_segment_ptr();  // QueryParams through short-lived views (see params_view)
+    const QueryParams& P0 = kernarg_view<QueryParams>(KP);
+    const int lane = static_cast<int>(threadIdx.x) & 63, wave = static_cast<int>(threadIdx.x) >> 6;
+    float* q = reinterpret_cast<float*>(smem + static_cast<size_t>(wave) * P0.tr.lds_per_wave);
+    uint2* stack = reinterpret_cast<uint2*>(q + kQueueFloats);
+    const uint64_t chunks = (P0.tr.n + 63) / 64;
+    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
+    for (uint64_t chunk = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave; chunk < chunks; chunk += stride) {
+        const QueryParams& Q = kernarg_view<QueryParams>(KP);  // one view per chunk of 64 rays
+        const TraceParams& P = Q.tr;
+        const uint64_t i = chunk * 64 + lane;
+        const bool act = i < P.n;
+        // effective bound: NaN and tmax <= 0 give b = 0 (a miss, not walked); +inf and anything above give f32::MAX
+        float b = 0.0f;
+        if (act) {
+            const float tm = Q.tmax ? Q.tmax[i] : FLT_MAX;
+            b = tm > 0.0f ? fminf(tm, FLT_MAX) : 0.0f;
+        }
+        const bool walk = b > 0.0f;
+        Ray r0;
+        r0.ox = r0.oy = r0.oz = r0.dx = r0.dy = r0.dz = r0.ix = r0.iy = r0.iz = 0.0f;
+        if (walk) ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r0);
+        if (P.scene.kind == 1u) {  // Sphere: a hit counts below b (primitives.rs:16-48)
+            if (act) {
+                float t = FLT_MAX, nn[3] = {0, 0, 0};
+                const bool hit = walk && sphere_intersect(P.scene, r0, t, nn) && t < b;
+                if (!hit) t = FLT_MAX;
+                if (MODE == kAnyHit) Q.occluded[i] = hit ? 1u : 0u;
+                else store_sphere_hit(P, i, r0, hit, t, nn);
+            }
+            continue;
+        }
+        GroupHit gh;
+        trace_objects<OBJ, true, MODE>(P.scene, r0, walk, q, stack, gh, b);
+        if (act) {
+            if (MODE == kAnyHit) Q.occluded[i] = gh.prim != kNoPrim ? 1u : 0u;
+            else store_group_hit<OBJ>(P, i, gh);
         }
     }
 }
@@ -3018,6 +3187,32 @@ int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, cons
     if (sc.inst_count != 0u) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
     else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
     return check(hipGetLastError(), "trace_rays_kernel launch", err);
+}
+
+// grid and LDS as launch_trace_rays; occluded != NULL: the any-hit kernel (hits unused), otherwise the bounded closest hit
+int launch_query_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                      const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count,
+                      void* stream, std::string& err) {
+    if (n == 0) return MP_OK;
+    QueryParams P;
+    P.tr.scene = sc;
+    P.tr.ox = ox; P.tr.oy = oy; P.tr.oz = oz; P.tr.dx = dx; P.tr.dy = dy; P.tr.dz = dz;
+    P.tr.n = n;
+    P.tr.hits = hits ? *hits : mp_hits_soa{};
+    P.tr.lds_per_wave = lds_bytes_per_wave(sc.stack_cap);
+    P.tmax = tmax;
+    P.occluded = occluded;
+    const uint32_t lds = P.tr.lds_per_wave * 4;
+    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
+    const uint64_t chunks = (n + 63) / 64, want = (chunks + 3) / 4;
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(cu_count) * 8));
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool obj = sc.inst_count != 0u;
+    if (occluded && obj) hipLaunchKernelGGL((query_rays_kernel<true, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
+    else if (occluded) hipLaunchKernelGGL((query_rays_kernel<false, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
+    else if (obj) hipLaunchKernelGGL((query_rays_kernel<true, kBounded>), dim3(grid), dim3(256), lds, st, P);
+    else hipLaunchKernelGGL((query_rays_kernel<false, kBounded>), dim3(grid), dim3(256), lds, st, P);
+    return check(hipGetLastError(), "query_rays_kernel launch", err);
 }
 
 int launch_set_u64(unsigned long long* d_ptr, unsigned long long value, void* stream, std::string& err) {

@@ -153,10 +153,21 @@ class TriangleBvh:
         )
         return (inner, packets, shading, vn, vt, mat) if with_material else (inner, packets, shading, vn, vt)
 
-    def intersect(self, origins, directions, stream=None, full: bool = False):
+    def _tmax(self, tmax, n, dev):
+        """per-ray bound as a float32 device tensor [n] (a Python float is rounded to f32 once and used for every ray)"""
+        import torch
+
+        if isinstance(tmax, torch.Tensor):
+            assert tmax.is_cuda and tmax.dtype == torch.float32 and tmax.shape == (n,), "tmax: float32 CUDA tensor [n]"
+            return tmax.contiguous()
+        return torch.full((n,), float(tmax), dtype=torch.float32, device=dev)
+
+    def intersect(self, origins, directions, stream=None, full: bool = False, tmax=None):
         """impl Object for TriangleBvh::intersect (ray_bvh_intersection.rs:26-96), batched over CUDA/HIP tensors.
 
         origins, directions: float32 torch tensors [n,3] on this context's GPU (directions need not be unit).
+        tmax: None (mp_trace_rays, unbounded), or a float32 CUDA tensor [n] / a Python float: the bounded closest hit
+        (mp_trace_rays_bounded): a hit only with t < min(tmax, f32::MAX); NaN or tmax <= 0 is a miss.
         Returns dict of device tensors: t, prim, u, v (+ point, normal, tex when full=True)."""
         import torch
 
@@ -183,13 +194,48 @@ class TriangleBvh:
             out["instance"] = torch.empty(n, dtype=torch.int32, device=dev)
             hits.d_instance = out["instance"].data_ptr()
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        if tmax is None:
+            _lib.check(
+                _lib.lib().mp_trace_rays(
+                    self.ctx.handle, self.handle, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), d[0].data_ptr(),
+                    d[1].data_ptr(), d[2].data_ptr(), n, C.byref(hits), C.c_void_p(st),
+                )
+            )
+            return out
+        tm = self._tmax(tmax, n, dev)
         _lib.check(
-            _lib.lib().mp_trace_rays(
+            _lib.lib().mp_trace_rays_bounded(
                 self.ctx.handle, self.handle, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), d[0].data_ptr(),
-                d[1].data_ptr(), d[2].data_ptr(), n, C.byref(hits), C.c_void_p(st),
+                d[1].data_ptr(), d[2].data_ptr(), tm.data_ptr(), n, C.byref(hits), C.c_void_p(st),
             )
         )
         return out
+
+    def occluded(self, origins, directions, tmax=None, stream=None):
+        """Any-hit (occlusion) query (mp_occluded_rays): True where the bounded closest-hit walk with bound
+        min(tmax, f32::MAX) would report a hit -- exactly, for every ray and bound -- found by a walk that stops at the first
+        accepted triangle.  tmax: None (f32::MAX for every ray), a float32 CUDA tensor [n] or a Python float.
+        Returns a torch.bool device tensor [n]."""
+        import torch
+
+        if self.ctx is None:
+            raise _lib.MinipathError(1, "host-only BVH cannot be traced: pass a Context to with_obj/build")
+        assert origins.is_cuda and directions.is_cuda and origins.dtype == torch.float32
+        n = origins.shape[0]
+        o = origins.t().contiguous()
+        d = directions.t().contiguous()
+        dev = origins.device
+        occ = torch.empty(n, dtype=torch.uint8, device=dev)
+        tm = None if tmax is None else self._tmax(tmax, n, dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(
+            _lib.lib().mp_occluded_rays(
+                self.ctx.handle, self.handle, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(), d[0].data_ptr(),
+                d[1].data_ptr(), d[2].data_ptr(), tm.data_ptr() if tm is not None else None, n, occ.data_ptr(),
+                C.c_void_p(st),
+            )
+        )
+        return occ.view(torch.bool)
 
     def close(self):
         if getattr(self, "handle", None):
