@@ -876,7 +876,7 @@ __device__ unsigned long long g_prof[4];
 #define MP_LEAF_ENTRIES 128
 #endif
 constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // direct-mapped: node index & 511 ; entry = node << 8 | mask
-constexpr int kMaskCacheHeader = 32;                        // B: [0..11] origin / inverse-direction bounds, [12] = sign pattern | 0x100 when valid (0xFFFFFFFF: none), [16..21] direction bounds
+constexpr int kMaskCacheHeader = 32;                        // B: [0..11] origin / inverse-direction bounds, [12] = sign pattern | 0x100 when valid (0xFFFFFFFF: none), [13..18] direction bounds
 constexpr int kLeafCacheEntries = MP_LEAF_ENTRIES;                      // direct-mapped: first packet of the leaf & 127 ; tag = first packet, mask = 64 bits (triangle i of the leaf)
 constexpr int kLeafTagBase = kMaskCacheHeader + kMaskCacheEntries;
 constexpr int kLeafMaskBase = kLeafTagBase + kLeafCacheEntries;   // uint2 per entry (8-byte aligned)
@@ -904,31 +904,52 @@ __device__ __forceinline__ void wave_min3_max3(float (&mn)[3], float (&mx)[3]) {
                  MP_DPP_STEP6("row_bcast:31 row_mask:0xc bank_mask:0xf")
                  : "+v"(mn[0]), "+v"(mn[1]), "+v"(mn[2]), "+v"(mx[0]), "+v"(mx[1]), "+v"(mx[2]));
 }
-// Called once per pass, before a sign-specialised walk with pattern `oct`: makes the cache's bounds B contain this pass's rays
-// (widening B and clearing the masks if they do not).  Returns false when the pass cannot use the cache: a non-finite inverse
-// direction, an origin beyond 2^30 or a direction component beyond 2 in magnitude (tri_may_hit's no-overflow argument).
-// B = origin, inverse-direction and direction bounds; three groups of (3 minima, 3 maxima), header slots g*6 .. g*6+5 for the first
-// two and 16..21 for the directions.
-__device__ __forceinline__ bool mask_cache_begin_pass(const MaskCache& mc, const Ray& r, bool active, uint32_t oct) {
+// Whether a ray may use the cached walk: every origin component within 2^30, every inverse-direction component finite and every
+// direction component within 2 in magnitude (tri_may_hit's no-overflow argument).  In the vector domain, branch-free: for any f32 x
+// (NaN included: its magnitude bits lie above +inf's) and any c >= 0, |x| <= c  <=>  (bits(x) & 0x7FFFFFFF) <= bits(c), and for
+// m, C in [0, 2^31 - 1), m <= C  <=>  m - (C + 1) is negative as a 32-bit integer: the three tests are the sign of one AND.
+__device__ __forceinline__ bool mask_cache_ray_ok(const Ray& r) {
+    constexpr uint32_t kMag = 0x7FFFFFFFu;
+    const uint32_t mo = max(max(as_u(r.ox) & kMag, as_u(r.oy) & kMag), as_u(r.oz) & kMag);
+    const uint32_t mi = max(max(as_u(r.ix) & kMag, as_u(r.iy) & kMag), as_u(r.iz) & kMag);
+    const uint32_t md = max(max(as_u(r.dx) & kMag, as_u(r.dy) & kMag), as_u(r.dz) & kMag);
+    constexpr uint32_t kCapO = 0x4E800000u /* 2^30 */, kCapI = 0x7F7FFFFFu /* FLT_MAX */, kCapD = 0x40000000u /* 2.0 */;
+    static_assert(kCoordCap == 1073741824.0f, "kCapO is kCoordCap's bit pattern");
+    return static_cast<int32_t>((mo - (kCapO + 1u)) & (mi - (kCapI + 1u)) & (md - (kCapD + 1u))) < 0;
+}
+// Called once per pass, before a sign-specialised walk with pattern `oct`, for a pass whose every active ray passed
+// mask_cache_ray_ok: makes the cache's bounds B contain this pass's rays (widening B and clearing the masks if they do not).
+// B = origin, inverse-direction and direction bounds; three groups of (3 minima, 3 maxima) in header slots hdr_lo(g) .. + 5.
+// The header (slots 0..19) is read with five 16-byte LDS loads (the wave's base is 16-byte aligned: kMaskCacheDwords % 4 == 0, the
+// per-wave LDS sizes of both cached kernels are multiples of 16 bytes, and smem is __align__(16)).
+constexpr int kHdrState = 12;                     // sign pattern | 0x100 while B is valid (0xFFFFFFFF: none)
+constexpr int hdr_lo(int g) { return g == 2 ? kHdrState + 1 : g * 6; }  // group g's minima; its maxima follow at + 3
+__device__ __forceinline__ void mask_cache_begin_pass(const MaskCache& mc, const Ray& r, bool active, uint32_t oct) {
     const int lane = static_cast<int>(threadIdx.x) & 63;
-    const bool fin = fabsf(r.ox) <= kCoordCap && fabsf(r.oy) <= kCoordCap && fabsf(r.oz) <= kCoordCap && fabsf(r.ix) < INFINITY &&
-                     fabsf(r.iy) < INFINITY && fabsf(r.iz) < INFINITY && fabsf(r.dx) <= 2.0f && fabsf(r.dy) <= 2.0f && fabsf(r.dz) <= 2.0f;
-    if (__ballot(active && !fin) != 0) return false;
     float* hdr = reinterpret_cast<float*>(mc.lds);
-    const uint32_t state = __builtin_amdgcn_readfirstlane(mc.lds[12]);
+    float h[20];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const float4 q = reinterpret_cast<const float4*>(mc.lds)[i];
+        h[4 * i] = q.x; h[4 * i + 1] = q.y; h[4 * i + 2] = q.z; h[4 * i + 3] = q.w;
+    }
+    const uint32_t state = __builtin_amdgcn_readfirstlane(as_u(h[kHdrState]));
     const bool same = state == (oct | 0x100u);
     const float val[3][3] = {{r.ox, r.oy, r.oz}, {r.ix, r.iy, r.iz}, {r.dx, r.dy, r.dz}};
-    // P inside B ?  Every active lane compares its own ray with the header: no reduction in the common case
-    bool viol = !same;
-    if (same) {
+    // P inside B ?  Every active lane compares its own ray with the header: no reduction in the common case.  For finite v and
+    // finite lo <= hi, med3(v, lo, hi) is v itself when lo <= v <= hi (up to the sign of a zero) and lo or hi otherwise, and the
+    // difference of two finite numbers is +-0 exactly when they are equal (denormals are kept): v < lo || v > hi  <=>
+    // v - med3(v, lo, hi) != 0.  The nine differences are folded with maxNum of magnitudes (never NaN: all operands finite).
+    float dev = 0.0f;
 #pragma unroll
-        for (int g = 0; g < 3; g++) {
-            const int base = g == 2 ? 16 : g * 6;
+    for (int g = 0; g < 3; g++) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) viol = viol || val[g][k] < hdr[base + k] || val[g][k] > hdr[base + 3 + k];
+        for (int k = 0; k < 3; k++) {
+            const float v = val[g][k];
+            dev = fmaxf(dev, fabsf(v - __builtin_amdgcn_fmed3f(v, h[hdr_lo(g) + k], h[hdr_lo(g) + 3 + k])));
         }
     }
-    if (__ballot(active && viol) != 0) {
+    if (__ballot(active && (!same || dev != 0.0f)) != 0) {
         float pmin[3][3], pmax[3][3];  // after the reductions: lane 63 holds the wave's bounds
 #pragma unroll
         for (int g = 0; g < 3; g++) {
@@ -944,11 +965,10 @@ __device__ __forceinline__ bool mask_cache_begin_pass(const MaskCache& mc, const
         // within 2^31 and direction bounds within 2: every pass that gets here lies well inside)
 #pragma unroll
         for (int g = 0; g < 3; g++) {
-            const int base = g == 2 ? 16 : g * 6;
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 float lo = pmin[g][k], hi = pmax[g][k];
-                if (same) { lo = fminf(lo, hdr[base + k]); hi = fmaxf(hi, hdr[base + 3 + k]); }
+                if (same) { lo = fminf(lo, h[hdr_lo(g) + k]); hi = fmaxf(hi, h[hdr_lo(g) + 3 + k]); }
                 const float pad = (hi - lo) * MP_MCACHE_PAD;
                 float wlo = lo - pad, whi = hi + pad;
                 if (g == 1) {  // same sign as the pass's inverse directions (all of one sign, finite, non-zero)
@@ -968,11 +988,10 @@ __device__ __forceinline__ bool mask_cache_begin_pass(const MaskCache& mc, const
         if (lane == 63) {
 #pragma unroll
             for (int g = 0; g < 3; g++) {
-                const int base = g == 2 ? 16 : g * 6;
 #pragma unroll
-                for (int k = 0; k < 3; k++) { hdr[base + k] = pmin[g][k]; hdr[base + 3 + k] = pmax[g][k]; }
+                for (int k = 0; k < 3; k++) { hdr[hdr_lo(g) + k] = pmin[g][k]; hdr[hdr_lo(g) + 3 + k] = pmax[g][k]; }
             }
-            mc.lds[12] = oct | 0x100u;
+            mc.lds[kHdrState] = oct | 0x100u;
         }
         int l_ = lane;  // (re-derived here: the clear runs once per unit, its address is not worth a register across the walk)
         asm volatile("" : "+v"(l_));
@@ -980,7 +999,6 @@ __device__ __forceinline__ bool mask_cache_begin_pass(const MaskCache& mc, const
         for (int i = 0; i < (kMaskCacheEntries + kLeafCacheEntries) / 64; i++) mc.lds[kMaskCacheHeader + i * 64 + l_] = 0xFFFFFFFFu;  // no node / leaf has this tag
         wave_lds_sync();
     }
-    return true;
 }
 // lane j (0..7): can any ray with origin / inverse direction inside the bounds `b` (omin[3], omax[3], imin[3], imax[3]) pass child
 // j's box {bmn, bmx}?  (see above)
@@ -1033,7 +1051,7 @@ __device__ __forceinline__ Iv iv_fma(const Iv a, const Iv b, const Iv z) {  // f
 }
 // can any ray with origin / direction inside the bounds `b` (mask-cache header) hit the triangle {v0, e1, e2}?
 __device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3], const float (&e1)[3], const float (&e2)[3]) {
-    const Iv d[3] = {Iv{b[16], b[19]}, Iv{b[17], b[20]}, Iv{b[18], b[21]}};
+    const Iv d[3] = {Iv{b[13], b[16]}, Iv{b[14], b[17]}, Iv{b[15], b[18]}};
     // h = (fms(dy, e2z, dz * e2y), fms(dz, e2x, dx * e2z), fms(dx, e2y, dy * e2x)) ; fms(a, b, c) = fma(a, b, -c)
     const Iv h[3] = {iv_fma_c(d[1], e2[2], iv_neg(iv_mul_c(d[2], e2[1]))), iv_fma_c(d[2], e2[0], iv_neg(iv_mul_c(d[0], e2[2]))),
                      iv_fma_c(d[0], e2[1], iv_neg(iv_mul_c(d[1], e2[0])))};
@@ -1340,9 +1358,20 @@ __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ra
                 const float tn = fma_dot(e2x, e2y, e2z, qx, qy, qz);
                 const float xv = det_ok ? as_f(as_u(vn) ^ det_sign) : 1.0f, xt = det_ok ? as_f(as_u(tn) ^ det_sign) : 1.0f;
                 if (__ballot(!(fminf(fminf(xu, xv), xt) <= thr)) == 0) return;
-                const float inv_det = 1.0f / det;
+                // inv_det = 1 / det (:201) through rm::rcp_short when every lane's |det| lies in its window [2^-94, 2^125] (ray_math.h:
+                // there the short sequence is the IEEE division's own, minus range fix-ups that do nothing, so inv_det is the same
+                // number); otherwise the whole wave divides.  Only live rays need the window (the others cannot accept: t < lim < 0
+                // fails); testing every lane is stricter and keeps the guard at one compare and a branch on VCC.  The test is on the
+                // magnitude bits: bits(det) << 1 drops the sign and keeps the order of |det| (NaN above +inf), and one unsigned compare
+                // of the offset checks both ends: +-0, denormals, tiny, huge, inf and NaN all fall outside.
+                constexpr uint32_t kRcpLo = 0x10800000u /* 2^-94 */, kRcpHi = 0x7E000000u /* 2^125 */;
+                const uint32_t wkey = (as_u(det) << 1) - (kRcpLo << 1);
+                const float inv_det = __ballot(wkey > ((kRcpHi - kRcpLo) << 1)) == 0 ? rm::rcp_short(det) : 1.0f / det;
                 const float u = inv_det * un, v = inv_det * vn, t = inv_det * tn;
-                const bool acc = (u >= 0.0f) & (v >= 0.0f) & ((u + v) <= 1.0f) & (t >= 0.0f) & (t < lim);  // :125, :129, :59
+                // :125, :129, :59 -- (u >= 0) & (v >= 0) & (u + v <= 1) & (t >= 0) & (t < lim) in fewer compares.  Without NaN operands
+                // minNum is the minimum and `< 0` is false for -0, as `-0 >= 0` is true; a NaN in u or v makes u + v NaN and fails the
+                // sum test, a NaN in t fails `t < lim`, so the cases where minNum drops a NaN operand are decided by the other tests.
+                const bool acc = !(fminf(fminf(u, v), t) < 0.0f) & ((u + v) <= 1.0f) & (t < lim);
                 best_t = acc ? t : best_t;
                 lim = acc ? t : lim;
                 bu = acc ? u : bu;
@@ -1390,28 +1419,40 @@ __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ra
 template <bool OCTANTS, class Stack, bool MC = false>
 __device__ __forceinline__ void trace_packet(const DevScene& sc, const Ray& r, bool active, Stack& st, PacketHit& hit,
                                              const MaskCache& mc = MaskCache{nullptr}) {
-    const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
-    if (__ballot(slow) != 0) {
-        trace_packet_impl<2, -1>(sc, r, active, st, hit);
-        return;
+    if (OCTANTS && MC) {
+        // Kernels with a mask cache: the sign-specialised walks use it, and a pass with a ray that fails mask_cache_ray_ok takes a
+        // generic walk.  The same choices as below, in another order: a ray with an infinite inverse component fails
+        // mask_cache_ray_ok, so a pass where every active ray passes is not `slow`; a pass where one fails takes the literal walk
+        // if it is slow and the generic MODE 1 walk otherwise (below, whether its signs are uniform or not).
+        if (__ballot(active & !mask_cache_ray_ok(r)) != 0) {
+            const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
+            if (__ballot(slow) != 0) trace_packet_impl<2, -1>(sc, r, active, st, hit);
+            else trace_packet_impl<1, -1>(sc, r, active, st, hit);
+            return;
+        }
+    } else {
+        const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
+        if (__ballot(slow) != 0) {
+            trace_packet_impl<2, -1>(sc, r, active, st, hit);
+            return;
+        }
     }
     if (OCTANTS && sc.boxes_ordered) {
         const uint64_t am = __ballot(active);
         const uint64_t nx = __ballot(active && r.ix < 0.0f), ny = __ballot(active && r.iy < 0.0f), nz = __ballot(active && r.iz < 0.0f);
         if ((nx == 0 || nx == am) && (ny == 0 || ny == am) && (nz == 0 || nz == am)) {
             const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-            if (MC) {  // kernels with a mask cache: the sign-specialised walks use it; a pass with a non-finite component takes the generic walk
-                if (mask_cache_begin_pass(mc, r, active, oct)) {
-                    switch (oct) {
-                        case 0: trace_packet_cached<0>(sc, r, active, hit, mc.lds); return;
-                        case 1: trace_packet_cached<1>(sc, r, active, hit, mc.lds); return;
-                        case 2: trace_packet_cached<2>(sc, r, active, hit, mc.lds); return;
-                        case 3: trace_packet_cached<3>(sc, r, active, hit, mc.lds); return;
-                        case 4: trace_packet_cached<4>(sc, r, active, hit, mc.lds); return;
-                        case 5: trace_packet_cached<5>(sc, r, active, hit, mc.lds); return;
-                        case 6: trace_packet_cached<6>(sc, r, active, hit, mc.lds); return;
-                        default: trace_packet_cached<7>(sc, r, active, hit, mc.lds); return;
-                    }
+            if (MC) {  // kernels with a mask cache: the sign-specialised walks use it
+                mask_cache_begin_pass(mc, r, active, oct);
+                switch (oct) {
+                    case 0: trace_packet_cached<0>(sc, r, active, hit, mc.lds); return;
+                    case 1: trace_packet_cached<1>(sc, r, active, hit, mc.lds); return;
+                    case 2: trace_packet_cached<2>(sc, r, active, hit, mc.lds); return;
+                    case 3: trace_packet_cached<3>(sc, r, active, hit, mc.lds); return;
+                    case 4: trace_packet_cached<4>(sc, r, active, hit, mc.lds); return;
+                    case 5: trace_packet_cached<5>(sc, r, active, hit, mc.lds); return;
+                    case 6: trace_packet_cached<6>(sc, r, active, hit, mc.lds); return;
+                    default: trace_packet_cached<7>(sc, r, active, hit, mc.lds); return;
                 }
             } else {
                 switch (oct) {
@@ -1713,7 +1754,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
         float acc, cnt;  // pixel_sum (r=g=b) and alpha (worker.rs:40)
         pixel_state_load(P, off, inpix, sub == 0, acc, cnt);
         if (MCACHE) {  // a new unit: other pixels, other bounds
-            if (lane == 0) mc.lds[12] = 0xFFFFFFFFu;
+            if (lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;
             wave_lds_sync();
         }
         // passes are aligned to multiples of S in the absolute sample index, so that a chunk boundary (MP_FLAG_CHUNKED_SUM) never
@@ -1989,7 +2030,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MP_PATHS_WP
         if (RGB) pixel_state_load3(P, off, inpix, reinterpret_cast<float (&)[3]>(acc[0]), cnt);
         else pixel_state_load(P, off, inpix, sub == 0, acc[0], cnt);
         if (MCACHE) {  // a new unit: other pixels, other bounds
-            if (lane == 0) mc.lds[12] = 0xFFFFFFFFu;
+            if (lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;
             wave_lds_sync();
         }
         // passes are aligned to multiples of S in the absolute sample index, so that a chunk boundary (MP_FLAG_CHUNKED_SUM) never
