@@ -1,0 +1,298 @@
+// The packet walk's per-work-unit mask cache (kernels.hip, trace_packet_cached): the bounds B of a unit's rays, the predicates that
+// prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
+// that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
+// per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define
+// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_NODE_ENTRIES / MP_LEAF_ENTRIES before including it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#ifndef MP_PROF_COUNT
+#define MP_PROF_COUNT(i) do { } while (0)
+#endif
+
+namespace mp {
+namespace mc {
+__device__ __forceinline__ float as_f(uint32_t u) { return __uint_as_float(u); }
+__device__ __forceinline__ uint32_t as_u(float f) { return __float_as_uint(f); }
+
+// LDS traffic between lanes of ONE wavefront: DS operations of a wave execute in issue order, so only the
+// compiler has to be kept from reordering them.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct Ray {
+    float ox, oy, oz, dx, dy, dz, ix, iy, iz;
+};
+
+// util/simba.rs:57-59
+__device__ __forceinline__ float fma_dot(float ax, float ay, float az, float bx, float by, float bz) {
+    return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
+}
+// util/simba.rs:61-67 : mul_sub(a, b, c) = a*b - c, c rounded first
+__device__ __forceinline__ float fms(float a, float b, float c) { return __builtin_fmaf(a, b, -c); }
+
+// OCT >= 0: every ray of the wave has a finite inverse direction with the sign pattern OCT (bit 0: x < 0, bit 1: y < 0,
+// bit 2: z < 0) and the box is ordered (min <= max, checked at upload).  IEEE subtraction and multiplication by a constant are
+// monotone, so (bmin - o) * inv <= (bmax - o) * inv for inv > 0 and >= for inv < 0, and no 0 * inf can arise: the min / max of
+// aabb.rs:269-271 select the near / far plane the sign names, and the six min/max drop out of the compiled code.
+template <bool PATCH_NAN, int OCT>
+__device__ __forceinline__ void slab(float bnx, float bny, float bnz, float bxx, float bxy, float bxz, const Ray& r,
+                                     float limit, float& t1, float& t2) {
+    // aabb.rs:254-284
+    float ax = (bnx - r.ox) * r.ix, ay = (bny - r.oy) * r.iy, az = (bnz - r.oz) * r.iz;
+    float cx = (bxx - r.ox) * r.ix, cy = (bxy - r.oy) * r.iy, cz = (bxz - r.oz) * r.iz;
+    if (PATCH_NAN) {  // only rays with an infinite inverse direction component can produce 0*inf; maxNum/minNum drop a NaN operand
+        ax = fmaxf(ax, -INFINITY); ay = fmaxf(ay, -INFINITY); az = fmaxf(az, -INFINITY);
+        cx = fminf(cx, INFINITY); cy = fminf(cy, INFINITY); cz = fminf(cz, INFINITY);
+    }
+    float lox, loy, loz, hix, hiy, hiz;
+    if (OCT >= 0) {
+        lox = (OCT & 1) ? cx : ax; hix = (OCT & 1) ? ax : cx;
+        loy = (OCT & 2) ? cy : ay; hiy = (OCT & 2) ? ay : cy;
+        loz = (OCT & 4) ? cz : az; hiz = (OCT & 4) ? az : cz;
+    } else {
+        lox = fminf(ax, cx); loy = fminf(ay, cy); loz = fminf(az, cz);
+        hix = fmaxf(ax, cx); hiy = fmaxf(ay, cy); hiz = fmaxf(az, cz);
+    }
+    t1 = fmaxf(fmaxf(lox, 0.0f), fmaxf(loy, loz));
+    t2 = fminf(fminf(hix, limit), fminf(hiy, hiz));
+}
+
+// ---- packet-level child rejection with a per-unit mask cache (round 3) ----------------------------------------------------------
+// Counted on the metric's frame (tools/sim_collapse.py --packet-studies; profiles/r03_notes.md): a 64-ray camera packet tests 110
+// child boxes per pass and pushes 19; for 90 of the 91 others NO ray of the packet can pass, and a conservative test on bounds of
+// the packet -- componentwise min / max of the origins and inverse directions -- proves it.  Evaluating that test per node visit
+// (lane j = child j, the records through a vector load) was built first and ran slower than it saved (profiles/r03_notes.md).
+// What pays is doing it ONCE PER WORK UNIT: a unit shoots 8-16 passes through the same 2-4 pixels, and one set of bounds B that
+// contains every pass's rays gives one 8-bit "children that may be hit" mask per node, cached in LDS (the packet kernel uses no
+// other LDS).  Every pass checks, lane by lane, that its ray lies inside B (no reduction), and while that holds and the sign
+// pattern is the same, a node visit costs one LDS lookup and the exact per-ray slab tests of the surviving children only.  B starts
+// as the bounds of the first pass (wave reductions) widened by MP_MCACHE_PAD of their extent; a pass that does not fit widens B and
+// clears the cache.
+// Why skipping a child whose bit is clear is exact.  Only in the sign-specialised walks (OCT >= 0: every active ray has finite
+// inverse directions of one sign pattern) and only if every active origin and inverse component is finite.  Axis with inv > 0
+// (aabb.rs:257-271 gives lo = fl(fl(bmin - o) * inv), hi = fl(fl(bmax - o) * inv)): with omax >= o for every ray,
+// y = fl(bmin - omax) <= fl(bmin - o) (IEEE subtraction is monotone), so lo >= fl(y * inv) (multiplication by a positive number is
+// monotone) >= min(fl(y * imin), fl(y * imax)) =: L (x -> fl(y * x) is monotone on [imin, imax]: its minimum sits at an end);
+// likewise hi <= max(fl(z * imin), fl(z * imax)) =: U with z = fl(bmax - omin).  Axis with inv < 0: lo comes from bmax and products
+// decrease with the first factor: L from z, U from y.  Every ray's t1 = max(lo.x, 0, lo.y, lo.z) >= T1 = max(L.x, L.y, L.z, 0) and
+// its t2 = min(hi.x, limit, hi.y, hi.z) <= T2 = min(U.x, U.y, U.z); T1 > T2 therefore means t1 > t2 for every ray whose origin and
+// inverse direction lie in B: the reference pushes the child for none of them (ray_bvh_intersection.rs:158).  No NaN can arise: all
+// inputs are finite, inv is never 0, and B's inverse bounds keep the sign of the pattern.
+#ifndef MP_MCACHE_PAD
+#define MP_MCACHE_PAD 0.25f  // widening of the unit's bounds on either side, in extents of the pass that sets them (A/B: 0.0625 .. 1, profiles/r03_notes.md)
+#endif
+// Table sizes (powers of two).  Counted on the metric's frame (tools/cache_miss_count.py, 16 passes per unit): 17.4 node-mask and 6.1
+// leaf-mask slow paths per unit, 1.08 bounds (re)sets; 256 / 256 entries: 22.8 and 5.1 (20.05 against 20.14 ms), 256 / 128: 20.23 ms.
+#ifndef MP_NODE_ENTRIES
+#define MP_NODE_ENTRIES 512
+#endif
+#ifndef MP_LEAF_ENTRIES
+#define MP_LEAF_ENTRIES 128
+#endif
+constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // direct-mapped: node index & 511 ; entry = node << 8 | mask
+constexpr int kMaskCacheHeader = 32;                        // B: [0..11] origin / inverse-direction bounds, [12] = sign pattern | 0x100 when valid (0xFFFFFFFF: none), [13..18] direction bounds
+constexpr int kLeafCacheEntries = MP_LEAF_ENTRIES;                      // direct-mapped: first packet of the leaf & 127 ; tag = first packet, mask = 64 bits (triangle i of the leaf)
+constexpr int kLeafTagBase = kMaskCacheHeader + kMaskCacheEntries;
+constexpr int kLeafMaskBase = kLeafTagBase + kLeafCacheEntries;   // uint2 per entry (8-byte aligned)
+constexpr int kMaskCacheDwords = kLeafMaskBase + 2 * kLeafCacheEntries;
+static_assert((kLeafMaskBase % 2) == 0 && (kMaskCacheDwords % 4) == 0, "LDS alignment of the leaf masks / of the next wave's header");
+constexpr float kCoordCap = 1073741824.0f;                  // 2^30: magnitude bound of ray origins and triangle vertices for the triangle masks (see tri_may_hit)
+struct MaskCache {
+    uint32_t* lds;  // this wave's header + entries, or nullptr: no packet-level rejection
+};
+// Wave-wide minima of N values and maxima of N values at once (every lane takes part; inactive rays hold the neutral element):
+// four DPP steps inside each row of 16, row_bcast15 / row_bcast31 across the rows, the totals end in LANE 63's registers (the
+// caller goes on in the vector domain and takes lane 63's verdict: the scalar registers would not fit beside the walk's).  The
+// independent chains are interleaved step by step, so no instruction reads a register the previous two instructions wrote (the
+// DPP read-after-VALU-write hazard needs two wait states) and no s_nop is spent.
+#define MP_DPP_STEP6(CTRL)                                                                                              \
+    "v_min_f32_dpp %0, %0, %0 " CTRL "\n\tv_min_f32_dpp %1, %1, %1 " CTRL "\n\tv_min_f32_dpp %2, %2, %2 " CTRL "\n\t"         \
+    "v_max_f32_dpp %3, %3, %3 " CTRL "\n\tv_max_f32_dpp %4, %4, %4 " CTRL "\n\tv_max_f32_dpp %5, %5, %5 " CTRL "\n\t"
+__device__ __forceinline__ void wave_min3_max3(float (&mn)[3], float (&mx)[3]) {
+    asm volatile("s_nop 1\n\t"  // the operands may come straight out of VALU instructions
+                 MP_DPP_STEP6("quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf")
+                 MP_DPP_STEP6("quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf")
+                 MP_DPP_STEP6("row_half_mirror row_mask:0xf bank_mask:0xf")
+                 MP_DPP_STEP6("row_mirror row_mask:0xf bank_mask:0xf")
+                 MP_DPP_STEP6("row_bcast:15 row_mask:0xa bank_mask:0xf")
+                 MP_DPP_STEP6("row_bcast:31 row_mask:0xc bank_mask:0xf")
+                 : "+v"(mn[0]), "+v"(mn[1]), "+v"(mn[2]), "+v"(mx[0]), "+v"(mx[1]), "+v"(mx[2]));
+}
+// Whether a ray may use the cached walk: every origin component within 2^30, every inverse-direction component finite and every
+// direction component within 2 in magnitude (tri_may_hit's no-overflow argument).  In the vector domain, branch-free: for any f32 x
+// (NaN included: its magnitude bits lie above +inf's) and any c >= 0, |x| <= c  <=>  (bits(x) & 0x7FFFFFFF) <= bits(c), and for
+// m, C in [0, 2^31 - 1), m <= C  <=>  m - (C + 1) is negative as a 32-bit integer: the three tests are the sign of one AND.
+__device__ __forceinline__ bool mask_cache_ray_ok(const Ray& r) {
+    constexpr uint32_t kMag = 0x7FFFFFFFu;
+    const uint32_t mo = max(max(as_u(r.ox) & kMag, as_u(r.oy) & kMag), as_u(r.oz) & kMag);
+    const uint32_t mi = max(max(as_u(r.ix) & kMag, as_u(r.iy) & kMag), as_u(r.iz) & kMag);
+    const uint32_t md = max(max(as_u(r.dx) & kMag, as_u(r.dy) & kMag), as_u(r.dz) & kMag);
+    constexpr uint32_t kCapO = 0x4E800000u /* 2^30 */, kCapI = 0x7F7FFFFFu /* FLT_MAX */, kCapD = 0x40000000u /* 2.0 */;
+    static_assert(kCoordCap == 1073741824.0f, "kCapO is kCoordCap's bit pattern");
+    return static_cast<int32_t>((mo - (kCapO + 1u)) & (mi - (kCapI + 1u)) & (md - (kCapD + 1u))) < 0;
+}
+// Called once per pass, before a sign-specialised walk with pattern `oct`, for a pass whose every active ray passed
+// mask_cache_ray_ok: makes the cache's bounds B contain this pass's rays (widening B and clearing the masks if they do not).
+// B = origin, inverse-direction and direction bounds; three groups of (3 minima, 3 maxima) in header slots hdr_lo(g) .. + 5.
+// The header (slots 0..19) is read with five 16-byte LDS loads (the wave's base is 16-byte aligned: kMaskCacheDwords % 4 == 0, the
+// per-wave LDS sizes of both cached kernels are multiples of 16 bytes, and smem is __align__(16)).
+constexpr int kHdrState = 12;                     // sign pattern | 0x100 while B is valid (0xFFFFFFFF: none)
+constexpr int hdr_lo(int g) { return g == 2 ? kHdrState + 1 : g * 6; }  // group g's minima; its maxima follow at + 3
+// P inside B ?  Every active lane compares its own ray with the header: no reduction in the common case.  For finite v and finite
+// lo <= hi, med3(v, lo, hi) is v itself when lo <= v <= hi (up to the sign of a zero) and lo or hi otherwise, and the difference of
+// two finite numbers is +-0 exactly when they are equal (denormals are kept): v < lo || v > hi  <=>  bounds_deviation(v, lo, hi) != 0.
+// mask_cache_begin_pass folds the nine deviations with maxNum (never NaN: all operands finite).  (The fold stays in the caller: as a
+// function of the nine values it schedules the flagship kernel's pass entry differently.)
+__device__ __forceinline__ float bounds_deviation(float v, float lo, float hi) {
+    return fabsf(v - __builtin_amdgcn_fmed3f(v, lo, hi));
+}
+__device__ __forceinline__ void mask_cache_begin_pass(const MaskCache& mc, const Ray& r, bool active, uint32_t oct) {
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    float* hdr = reinterpret_cast<float*>(mc.lds);
+    float h[20];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const float4 q = reinterpret_cast<const float4*>(mc.lds)[i];
+        h[4 * i] = q.x; h[4 * i + 1] = q.y; h[4 * i + 2] = q.z; h[4 * i + 3] = q.w;
+    }
+    const uint32_t state = __builtin_amdgcn_readfirstlane(as_u(h[kHdrState]));
+    const bool same = state == (oct | 0x100u);
+    const float val[3][3] = {{r.ox, r.oy, r.oz}, {r.ix, r.iy, r.iz}, {r.dx, r.dy, r.dz}};
+    float dev = 0.0f;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) dev = fmaxf(dev, bounds_deviation(val[g][k], h[hdr_lo(g) + k], h[hdr_lo(g) + 3 + k]));
+    }
+    if (__ballot(active && (!same || dev != 0.0f)) != 0) {
+        float pmin[3][3], pmax[3][3];  // after the reductions: lane 63 holds the wave's bounds
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                pmin[g][k] = active ? val[g][k] : INFINITY;
+                pmax[g][k] = active ? val[g][k] : -INFINITY;
+            }
+            wave_min3_max3(pmin[g], pmax[g]);
+        }
+        // new bounds: this pass's, united with the old ones when they belong to the same sign pattern, widened by MP_MCACHE_PAD of the extent
+        // (an inverse-direction bound never crosses zero: the sign pattern is part of the node masks' meaning; origin bounds stay
+        // within 2^31 and direction bounds within 2: every pass that gets here lies well inside)
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                float lo = pmin[g][k], hi = pmax[g][k];
+                if (same) { lo = fminf(lo, h[hdr_lo(g) + k]); hi = fmaxf(hi, h[hdr_lo(g) + 3 + k]); }
+                const float pad = (hi - lo) * MP_MCACHE_PAD;
+                float wlo = lo - pad, whi = hi + pad;
+                if (g == 1) {  // same sign as the pass's inverse directions (all of one sign, finite, non-zero)
+                    if ((wlo < 0.0f) != (lo < 0.0f) || wlo == 0.0f) wlo = lo;
+                    if ((whi < 0.0f) != (hi < 0.0f) || whi == 0.0f) whi = hi;
+                    if (!(fabsf(wlo) < INFINITY)) wlo = lo;
+                    if (!(fabsf(whi) < INFINITY)) whi = hi;
+                } else {
+                    const float cap = g == 0 ? 2.0f * kCoordCap : 2.0f;
+                    wlo = fmaxf(wlo, -cap); whi = fminf(whi, cap);
+                }
+                pmin[g][k] = wlo; pmax[g][k] = whi;
+            }
+        }
+        MP_PROF_COUNT(3);
+        wave_lds_sync();  // the reads above before the header is rewritten
+        if (lane == 63) {
+#pragma unroll
+            for (int g = 0; g < 3; g++) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) { hdr[hdr_lo(g) + k] = pmin[g][k]; hdr[hdr_lo(g) + 3 + k] = pmax[g][k]; }
+            }
+            mc.lds[kHdrState] = oct | 0x100u;
+        }
+        int l_ = lane;  // (re-derived here: the clear runs once per unit, its address is not worth a register across the walk)
+        asm volatile("" : "+v"(l_));
+#pragma unroll
+        for (int i = 0; i < (kMaskCacheEntries + kLeafCacheEntries) / 64; i++) mc.lds[kMaskCacheHeader + i * 64 + l_] = 0xFFFFFFFFu;  // no node / leaf has this tag
+        wave_lds_sync();
+    }
+}
+// lane j (0..7): can any ray with origin / inverse direction inside the bounds `b` (omin[3], omax[3], imin[3], imax[3]) pass child
+// j's box {bmn, bmx}?  (see above)
+template <int OCT>
+__device__ __forceinline__ bool bounds_may_hit(const float* b, const float bmn[3], const float bmx[3]) {
+    float L[3], U[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float y = bmn[k] - b[3 + k], z = bmx[k] - b[k];
+        const float lo_src = ((OCT >> k) & 1) ? z : y, hi_src = ((OCT >> k) & 1) ? y : z;
+        L[k] = fminf(lo_src * b[6 + k], lo_src * b[9 + k]);
+        U[k] = fmaxf(hi_src * b[6 + k], hi_src * b[9 + k]);
+    }
+    const float t1 = fmaxf(fmaxf(L[0], 0.0f), fmaxf(L[1], L[2])), t2 = fminf(U[0], fminf(U[1], U[2]));
+    return !(t1 > t2);
+}
+
+// ---- ... and packet-level TRIANGLE rejection with the same bounds --------------------------------------------------------------------
+// Counted on the metric's frame (tools/sim_tri_reject.py): a pass of 64 rays through two pixels tests 53 triangles and 3.8 of them are
+// hit by some ray; with the unit's bounds B (origins, directions) 41 of the 53 can be PROVEN missed by every ray inside B, once per
+// work unit and leaf: the leaf's 64-bit mask "triangle i may be hit" is cached next to the node masks and a pass tests the survivors.
+// The proof is the Moeller-Trumbore expression sequence of triangle.rs:183-217 itself, evaluated on intervals: every operation of
+// it (fl(a*b), fl(a*b+c), fl(a-b), fl(1/x) on an interval without zero) is monotone in each operand while the others are fixed, so
+// the same f32 operation evaluated at the corners of the operand intervals bounds the operation's result for every ray inside B --
+// no error analysis, the bounds contain the very f32 values the per-ray test computes.  A triangle is skipped when the bounds show
+// u < 0, v < 0, u + v > 1 or t < 0 for all of them (:125 then accepts for no ray).  No NaN can arise on the way: every origin bound
+// is within 2^31, every direction bound within 2, every vertex within 2^30 and every edge within 2^31 (DevScene::tris_bounded,
+// mask_cache_begin_pass), which keeps all intermediate bounds finite up to the reciprocal (|t numerator| < 2^98); a determinant
+// interval that touches zero or has an infinite reciprocal keeps the triangle; after that every value is one product of finite
+// numbers (never NaN), and the only sum (u + v) can at worst be inf - inf = NaN, which compares false and keeps the triangle.
+struct Iv {
+    float lo, hi;
+};
+__device__ __forceinline__ Iv iv_neg(const Iv a) { return Iv{-a.hi, -a.lo}; }
+__device__ __forceinline__ Iv iv_mul_c(const Iv a, const float c) {  // fl(a * c)
+    const float p = a.lo * c, q = a.hi * c;
+    return Iv{fminf(p, q), fmaxf(p, q)};
+}
+__device__ __forceinline__ Iv iv_mul(const Iv a, const Iv b) {  // fl(a * b)
+    const float p1 = a.lo * b.lo, p2 = a.lo * b.hi, p3 = a.hi * b.lo, p4 = a.hi * b.hi;
+    return Iv{fminf(fminf(p1, p2), fminf(p3, p4)), fmaxf(fmaxf(p1, p2), fmaxf(p3, p4))};
+}
+__device__ __forceinline__ Iv iv_fma_c(const Iv a, const float c, const Iv z) {  // fl(a * c + z)
+    return Iv{fminf(__builtin_fmaf(a.lo, c, z.lo), __builtin_fmaf(a.hi, c, z.lo)), fmaxf(__builtin_fmaf(a.lo, c, z.hi), __builtin_fmaf(a.hi, c, z.hi))};
+}
+__device__ __forceinline__ Iv iv_fma(const Iv a, const Iv b, const Iv z) {  // fl(a * b + z)
+    const float l1 = __builtin_fmaf(a.lo, b.lo, z.lo), l2 = __builtin_fmaf(a.lo, b.hi, z.lo), l3 = __builtin_fmaf(a.hi, b.lo, z.lo), l4 = __builtin_fmaf(a.hi, b.hi, z.lo);
+    const float h1 = __builtin_fmaf(a.lo, b.lo, z.hi), h2 = __builtin_fmaf(a.lo, b.hi, z.hi), h3 = __builtin_fmaf(a.hi, b.lo, z.hi), h4 = __builtin_fmaf(a.hi, b.hi, z.hi);
+    return Iv{fminf(fminf(l1, l2), fminf(l3, l4)), fmaxf(fmaxf(h1, h2), fmaxf(h3, h4))};
+}
+// can any ray with origin / direction inside the bounds `b` (mask-cache header) hit the triangle {v0, e1, e2}?
+__device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3], const float (&e1)[3], const float (&e2)[3]) {
+    const Iv d[3] = {Iv{b[13], b[16]}, Iv{b[14], b[17]}, Iv{b[15], b[18]}};
+    // h = (fms(dy, e2z, dz * e2y), fms(dz, e2x, dx * e2z), fms(dx, e2y, dy * e2x)) ; fms(a, b, c) = fma(a, b, -c)
+    const Iv h[3] = {iv_fma_c(d[1], e2[2], iv_neg(iv_mul_c(d[2], e2[1]))), iv_fma_c(d[2], e2[0], iv_neg(iv_mul_c(d[0], e2[2]))),
+                     iv_fma_c(d[0], e2[1], iv_neg(iv_mul_c(d[1], e2[0])))};
+    // fma_dot(a, b) = fma(az, bz, fma(ay, by, ax * bx))
+    const Iv det = iv_fma_c(h[2], e1[2], iv_fma_c(h[1], e1[1], iv_mul_c(h[0], e1[0])));
+    if (!(det.lo > 0.0f || det.hi < 0.0f)) return true;
+    const Iv inv = Iv{1.0f / det.hi, 1.0f / det.lo};
+    if (!(fabsf(inv.lo) < INFINITY && fabsf(inv.hi) < INFINITY)) return true;
+    const Iv s[3] = {Iv{b[0] - v0[0], b[3] - v0[0]}, Iv{b[1] - v0[1], b[4] - v0[1]}, Iv{b[2] - v0[2], b[5] - v0[2]}};
+    const Iv u = iv_mul(inv, iv_fma(s[2], h[2], iv_fma(s[1], h[1], iv_mul(s[0], h[0]))));
+    const Iv q[3] = {iv_fma_c(s[1], e1[2], iv_neg(iv_mul_c(s[2], e1[1]))), iv_fma_c(s[2], e1[0], iv_neg(iv_mul_c(s[0], e1[2]))),
+                     iv_fma_c(s[0], e1[1], iv_neg(iv_mul_c(s[1], e1[0])))};
+    const Iv v = iv_mul(inv, iv_fma(d[2], q[2], iv_fma(d[1], q[1], iv_mul(d[0], q[0]))));
+    const Iv t = iv_mul(inv, iv_fma_c(q[2], e2[2], iv_fma_c(q[1], e2[1], iv_mul_c(q[0], e2[0]))));
+    const bool miss = u.hi < 0.0f || v.hi < 0.0f || (u.lo + v.lo) > 1.0f || t.hi < 0.0f;
+    return !miss;
+}
+
+}  // namespace mc
+}  // namespace mp
