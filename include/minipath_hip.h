@@ -215,8 +215,14 @@ int mp_ctx_device(const mp_ctx *ctx, int *device_id, int *cu_count);
  * without MP_FLAG_WAVEFRONT; 1 default): 0 = one pass of 8 samples per walk of the bounce rays, 2 / 3 = two / up to four passes share
  * one walk over a per-wave ray queue in global memory (fewer idle lane groups at the end of every walk), 1 = the latter for scenes
  * whose traversal arrays exceed 1 MB.  "render_batch_tiles" (0 = automatic, default): tiles per launch of mp_render_begin's workers.
+ * "multi_gather_staged" (0 default, or 1; read on the gathering context, ctxs[0] of mp_render_frame_multi / mp_render_pass_multi):
+ * 1 = every rank but rank 0 sends its shard through pinned host memory, as between devices without peer access, even where a
+ * direct copy would do (two contexts on one device included).
  * Results never depend on any of them (tests sweep them). */
 int mp_ctx_set_option(mp_ctx *ctx, const char *key, int value);
+/* Diagnostics.  "multi_staged_ranks": ranks of the last frame gathered on ctx (as ctxs[0] of mp_render_frame_multi /
+ * mp_render_pass_multi) whose shard travelled through pinned host memory. */
+int mp_ctx_query(mp_ctx *ctx, const char *key, uint64_t *value);
 
 /* ---- camera.rs ------------------------------------------------------------------------------------------ */
 int mp_camera_default(mp_camera *cam);                                                            /* :42-52 */
@@ -378,8 +384,8 @@ int mp_untile(mp_ctx *ctx, const mp_settings *settings, const mp_block *tiles, s
               const float *d_tiles_f32, float *d_image_f32, uint8_t *d_image_u8, void *stream);
 /* Preview of an unfinished MP_FLAG_ACCUMULATE tile buffer after samples_done (< sample_count) samples, scattered into an
  * image-major frame like mp_untile; the buffer is only read.  BUILD-DEFINED (the reference's progressive consumer, gui.rs:216-224,
- * re-renders with a smaller sample_count instead): pixel = running sum * (1.0f / (f32)samples_done), alpha = hits * the same
- * (worker.rs:44 for the samples drawn so far); under MP_FLAG_CHUNKED_SUM (f32)((total + (f64)chunk sum) * (1.0 / (f64)samples_done)).
+ * re-renders with a smaller sample_count instead): each of r, g, b = its running sum * (1.0f / (f32)samples_done), alpha = hits *
+ * the same (worker.rs:44 for the samples drawn so far); under MP_FLAG_CHUNKED_SUM (f32)((total + (f64)chunk sum) * (1.0 / (f64)samples_done)).
  * samples_done == sample_count: the buffer already holds the means, plain mp_untile. */
 int mp_untile_preview(mp_ctx *ctx, const mp_settings *settings, const mp_block *tiles, size_t n_tiles,
                       const float *d_tiles_f32, uint32_t samples_done, float *d_image_f32, uint8_t *d_image_u8, void *stream);
@@ -398,7 +404,9 @@ int mp_render_frame_multi(mp_ctx *const *ctxs, const mp_scene *const *scenes, in
 /* Progressive form (BASELINE configs[4]; SURVEY 8e: "accumulators stay sharded; gather only per displayed pass / at end"):
  * settings carries MP_FLAG_ACCUMULATE and names the pass [pass_begin, pass_begin + pass_count).  Every rank adds the pass to the
  * running state of ITS shard, which stays on its device between calls (pass_begin must continue the previous call's pass with
- * the same settings, ranks and scenes; pass_begin 0 starts over).  gather = 0: nothing leaves the devices.  gather != 0: the
+ * the same settings, ranks and scenes; pass_begin 0 starts over).  A pass is all or nothing: every rank is checked before any
+ * launches, so a refused call leaves every shard's state as it was (a launch that fails once the ranks are enqueued resets them
+ * all: the next pass must start over from 0).  gather = 0: nothing leaves the devices.  gather != 0: the
  * shards are gathered and scattered as in mp_render_frame_multi -- after the last pass the finished frame (bit-identical to one
  * mp_render_frame_multi), after an earlier pass a preview as mp_untile_preview defines it (the shards keep their state). */
 int mp_render_pass_multi(mp_ctx *const *ctxs, const mp_scene *const *scenes, int n, const mp_camera_sampler *sampler,

@@ -82,6 +82,7 @@ struct mp_ctx {
     std::atomic<uint32_t> render_batch{0};    // tiles per launch of render() (0 = automatic)
     std::atomic<uint32_t> mask_cache{1};      // packet kernel: per-unit mask cache of the packet-level child rejection
     std::atomic<uint32_t> paths_pooled{1};    // path extension: 0 = render_paths_kernel, 1 = auto, 2 / 3 = always pooled (RenderLaunch::paths_pooled)
+    std::atomic<uint32_t> multi_gather_staged{0};  // as the gathering context: 1 = every rank but rank 0 staged through pinned host memory
     uint32_t* take_counter() {  // one set of work-queue heads per launch in flight
         return d_counters + static_cast<size_t>(next_counter.fetch_add(1, std::memory_order_relaxed) % kCounters) * kWorkQueues * kWorkQueueStride;
     }
@@ -142,6 +143,7 @@ struct mp_ctx {
         size_t gather_cap = 0;
         hipEvent_t untiled = nullptr;
         bool untiled_valid = false;
+        uint32_t staged_ranks = 0;  // as the gathering context: ranks of the last gathered frame staged through pinned host memory
         std::vector<int> peer;  // by device id: 0 = not asked yet, 1 = direct peer copies, 2 = staged through the host
         // progressive accumulation: what the shard's running state belongs to, and the next sample it expects
         uint64_t acc_seed = 0;
@@ -483,12 +485,20 @@ uint32_t pass_samples(const mp_settings& st) {
     return st.pass_count ? st.pass_count : st.sample_count - st.pass_begin;
 }
 
+// The refusals of render_tiles_device that the scene and the settings decide alone, before anything is launched (0 = none).
+int render_refusal(const mp_scene* scene, const mp_settings& st) {
+    if ((st.flags & MP_FLAG_PATHS) && (st.flags & MP_FLAG_CHUNKED_SUM) && scene->dev.materials_rgb)
+        return fail(MP_ERR_UNSUPPORTED, "coloured / textured materials are not combined with MP_FLAG_CHUNKED_SUM (its pixel state carries one channel)");
+    if ((st.flags & MP_FLAG_PATHS) && st.max_depth > 0 && scene->dev.kind != 0u)
+        return fail(MP_ERR_UNSUPPORTED, "the path extension is defined for TriangleBvh scenes only");
+    return MP_OK;
+}
+
 // Renders `tiles` into a tile-major device buffer (launch only).
 int render_tiles_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler& sampler, const mp_settings& st,
                         const mp_block* d_tiles, size_t n, float* d_out, void* stream, uint64_t* d_segments = nullptr,
                         const uint32_t* d_tile_order = nullptr, uint64_t* d_tile_cost = nullptr) {
-    if ((st.flags & MP_FLAG_PATHS) && (st.flags & MP_FLAG_CHUNKED_SUM) && scene->dev.materials_rgb)
-        return fail(MP_ERR_UNSUPPORTED, "coloured / textured materials are not combined with MP_FLAG_CHUNKED_SUM (its pixel state carries one channel)");
+    if (int rc = render_refusal(scene, st)) return rc;
     RenderLaunch L;
     L.scene = scene->dev;
     L.scene.packet_stack_regs = ctx->packet_stack_regs.load();
@@ -592,6 +602,11 @@ int mp_ctx_set_option(mp_ctx* ctx, const char* key, int value) {
         ctx->paths_pooled.store(static_cast<uint32_t>(value));
         return MP_OK;
     }
+    if (std::strcmp(key, "multi_gather_staged") == 0) {
+        if (value < 0 || value > 1) return fail(MP_ERR_INVALID, "multi_gather_staged must be 0 (direct copies where the devices reach each other) or 1 (through pinned host memory)");
+        ctx->multi_gather_staged.store(static_cast<uint32_t>(value));
+        return MP_OK;
+    }
     if (std::strcmp(key, "packet_rays_per_lane") == 0) {
         if (value != 1 && value != 2) return fail(MP_ERR_INVALID, "packet_rays_per_lane must be 1 or 2");
         ctx->rays_per_lane.store(static_cast<uint32_t>(value));
@@ -614,6 +629,18 @@ int mp_ctx_set_option(mp_ctx* ctx, const char* key, int value) {
         return MP_OK;
     }
     return fail(MP_ERR_INVALID, std::string("unknown option: ") + key);
+    });
+}
+
+int mp_ctx_query(mp_ctx* ctx, const char* key, uint64_t* value) {
+    return guarded([&]() -> int {
+    if (!ctx || !key || !value) return fail(MP_ERR_INVALID, "NULL argument");
+    if (std::strcmp(key, "multi_staged_ranks") == 0) {
+        std::lock_guard<std::mutex> lk(ctx->multi_mu);
+        *value = ctx->multi.staged_ranks;
+        return MP_OK;
+    }
+    return fail(MP_ERR_INVALID, std::string("unknown query: ") + key);
     });
 }
 
@@ -1214,9 +1241,35 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
             c0->multi.peer[static_cast<size_t>(d)] = direct ? 1 : 2;
         }
     }
+    // how each rank's shard reaches device 0, decided once for both legs of the copy
+    std::vector<char> staged(static_cast<size_t>(n), 0);
+    if (gather) {
+        const bool force = c0->multi_gather_staged.load() != 0u;
+        for (int r = 1; r < n; r++) {
+            const int d = ctxs[r]->device;
+            staged[static_cast<size_t>(r)] = force || (d != c0->device && c0->multi.peer[static_cast<size_t>(d)] == 2);
+        }
+    }
+    // A pass is all or nothing: every rank is checked before anything is launched, so a refusal leaves every shard as it was.
+    for (int r = 0; r < n; r++) {
+        mp_ctx* c = ctxs[r];
+        if (shard[static_cast<size_t>(r)].empty()) continue;
+        if (int rc = render_refusal(scenes[r], *settings)) return rc;
+        if (!acc || p_begin == 0) continue;
+        std::unique_lock<std::mutex> lk(c->multi_mu, std::defer_lock);
+        if (c != c0) lk.lock();
+        const mp_ctx::MultiBuf& m = c->multi;
+        // the running state in the shard must be this render's, at this sample (a shard that is too small has none)
+        const bool same = m.acc_seed == settings->seed && m.acc_w == settings->width && m.acc_h == settings->height && m.acc_ts == ts &&
+                          m.acc_spp == settings->sample_count && m.acc_flags == (settings->flags & ~0u) && m.acc_depth == settings->max_depth &&
+                          m.acc_n == static_cast<uint32_t>(n) && m.acc_rank == static_cast<uint32_t>(r) && m.acc_scene == scenes[r];
+        if (!(same && m.acc_next == p_begin && m.d_shard && m.shard_cap >= per_rank * tile_floats))
+            return fail(MP_ERR_INVALID, "progressive pass does not continue the state this rank's shard holds (pass_begin must be the previous pass's end, same settings, same ranks)");
+    }
     uint64_t segs = 0;
     // every rank renders its shard in one launch on its own stream (machinery.rs:51-116: the workers own their tiles) and, when
     // the frame is gathered, sends it to device 0 on that same stream: n copies on n streams, each peer over its own link
+    auto launch_ranks = [&]() -> int {
     for (int r = 0; r < n; r++) {
         mp_ctx* c = ctxs[r];
         const size_t nt = shard[static_cast<size_t>(r)].size();
@@ -1232,22 +1285,8 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
             if (m.d_shard) (void)hipFree(m.d_shard);
             m.d_shard = nullptr;
             m.shard_cap = 0;
-            m.acc_next = 0;
             MP_HIP(hipMalloc(reinterpret_cast<void**>(&m.d_shard), per_rank * tile_floats * 4));
             m.shard_cap = per_rank * tile_floats;
-        }
-        if (acc) {  // the running state in the shard must be this render's, at this sample
-            const bool same = m.acc_seed == settings->seed && m.acc_w == settings->width && m.acc_h == settings->height && m.acc_ts == ts &&
-                              m.acc_spp == settings->sample_count && m.acc_flags == (settings->flags & ~0u) && m.acc_depth == settings->max_depth &&
-                              m.acc_n == static_cast<uint32_t>(n) && m.acc_rank == static_cast<uint32_t>(r) && m.acc_scene == scenes[r];
-            if (p_begin != 0 && !(same && m.acc_next == p_begin))
-                return fail(MP_ERR_INVALID, "progressive pass does not continue the state this rank's shard holds (pass_begin must be the previous pass's end, same settings, same ranks)");
-            m.acc_seed = settings->seed; m.acc_w = settings->width; m.acc_h = settings->height; m.acc_ts = ts;
-            m.acc_spp = settings->sample_count; m.acc_flags = settings->flags; m.acc_depth = settings->max_depth;
-            m.acc_n = static_cast<uint32_t>(n); m.acc_rank = static_cast<uint32_t>(r); m.acc_scene = scenes[r];
-            m.acc_next = final_pass ? 0u : p_end;
-        } else {
-            m.acc_next = 0;
         }
         const mp_block* d_tiles = nullptr;
         mp_ctx::TileListRef keep;
@@ -1262,11 +1301,13 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
         if (c0->multi.untiled_valid) MP_HIP(hipStreamWaitEvent(m.stream, c0->multi.untiled, 0));
         float* dst = c0->multi.d_gather + static_cast<size_t>(r) * per_rank * tile_floats;
         const size_t bytes = nt * tile_floats * 4;
-        const bool staged = c->device != c0->device && c0->multi.peer[static_cast<size_t>(c->device)] == 2;
-        if (!staged) {
+        if (!staged[static_cast<size_t>(r)]) {
             MP_HIP(hipMemcpyPeerAsync(dst, c0->device, m.d_shard, c->device, bytes, m.stream));
         } else {
             if (m.stage_cap < per_rank * tile_floats) {
+                // the last frame's legs through the old buffer (this stream's, then device 0's before its un-tile) are done with it
+                MP_HIP(hipStreamSynchronize(m.stream));
+                if (c0->multi.untiled_valid) MP_HIP(hipEventSynchronize(c0->multi.untiled));
                 if (m.h_stage) (void)hipHostFree(m.h_stage);
                 m.h_stage = nullptr;
                 m.stage_cap = 0;
@@ -1277,6 +1318,26 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
         }
         MP_HIP(hipEventRecord(m.copied, m.stream));
     }
+    return MP_OK;
+    };
+    const int launched = launch_ranks();
+    // commit the shards' state only now that every rank's pass is enqueued; after a failed launch no shard's state is known
+    for (int r = 0; r < n; r++) {
+        mp_ctx* c = ctxs[r];
+        if (shard[static_cast<size_t>(r)].empty()) continue;
+        std::unique_lock<std::mutex> lk(c->multi_mu, std::defer_lock);
+        if (c != c0) lk.lock();
+        mp_ctx::MultiBuf& m = c->multi;
+        if (launched != MP_OK || !acc) {
+            m.acc_next = 0;
+            continue;
+        }
+        m.acc_seed = settings->seed; m.acc_w = settings->width; m.acc_h = settings->height; m.acc_ts = ts;
+        m.acc_spp = settings->sample_count; m.acc_flags = settings->flags; m.acc_depth = settings->max_depth;
+        m.acc_n = static_cast<uint32_t>(n); m.acc_rank = static_cast<uint32_t>(r); m.acc_scene = scenes[r];
+        m.acc_next = final_pass ? 0u : p_end;
+    }
+    if (launched != MP_OK) return launched;
     if (ray_segments) *ray_segments = segs;  // reference semantics only (0 with MP_FLAG_PATHS: use mp_render_tiles_device_counted)
     if (!gather) return MP_OK;
     DeviceGuard g0(c0->device);
@@ -1285,10 +1346,12 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
         const size_t nt = shard[static_cast<size_t>(r)].size();
         if (nt == 0) continue;
         MP_HIP(hipStreamWaitEvent(st0, c->multi.copied, 0));
-        if (c->device != c0->device && c0->multi.peer[static_cast<size_t>(c->device)] == 2)  // second leg of the staged copy
+        if (staged[static_cast<size_t>(r)])  // second leg of the staged copy
             MP_HIP(hipMemcpyAsync(c0->multi.d_gather + static_cast<size_t>(r) * per_rank * tile_floats, c->multi.h_stage, nt * tile_floats * 4,
                                   hipMemcpyHostToDevice, st0));
     }
+    c0->multi.staged_ranks = 0;
+    for (int r = 0; r < n; r++) c0->multi.staged_ranks += (staged[static_cast<size_t>(r)] && !shard[static_cast<size_t>(r)].empty()) ? 1u : 0u;
     const mp_block* d_order = nullptr;
     mp_ctx::TileListRef keep0;
     int rc = c0->device_tiles(order.data(), order.size(), nullptr, keep0, &d_order, nullptr);

@@ -2585,8 +2585,8 @@ __device__ __forceinline__ uint8_t to_u8(float c) {
 }
 
 // mode 0: the buffer holds finished pixels (means).  Preview of an unfinished MP_FLAG_ACCUMULATE buffer after k samples (the buffer
-// is only read): mode 1: slot = {sum, sum, sum, hits} -> {sum * inv_k, .., hits * inv_k} with inv_k = 1.0f / (float)k (worker.rs:44
-// for the samples drawn so far); mode 2 (MP_FLAG_CHUNKED_SUM): slot = {chunk sum, hits, f64 total} ->
+// is only read): mode 1: slot = {sum r, sum g, sum b, hits} (r = g = b for a grey table) -> each * inv_k with
+// inv_k = 1.0f / (float)k (worker.rs:44 for the samples drawn so far); mode 2 (MP_FLAG_CHUNKED_SUM): slot = {chunk sum, hits, f64 total} ->
 // (f32)((total + (f64)chunk sum) * (1.0 / (f64)k)), (f32)((f64)hits * (1.0 / (f64)k)) -- pixel_state_store's rule for k samples.
 __global__ __launch_bounds__(256) void untile_kernel(uint32_t width, uint32_t height, uint32_t ts, const mp_block* tiles,
                                                      uint32_t n_tiles, const float* src, float* img_f32, uint8_t* img_u8,
@@ -2600,9 +2600,8 @@ __global__ __launch_bounds__(256) void untile_kernel(uint32_t width, uint32_t he
         const uint32_t x = T.min_x + p % ts, y = T.min_y + p / ts;
         if (x >= T.max_x || y >= T.max_y || x >= width || y >= height) continue;
         float4 v = *reinterpret_cast<const float4*>(src + i * 4);
-        if (mode == 1u) {
-            const float m = v.x * inv_k;
-            v = make_float4(m, m, m, v.w * inv_k);
+        if (mode == 1u) {  // every channel on its own: a grey slot {m, m, m, a} gives {m*inv_k, m*inv_k, m*inv_k, a*inv_k}
+            v = make_float4(v.x * inv_k, v.y * inv_k, v.z * inv_k, v.w * inv_k);
         } else if (mode == 2u) {
             const double tot = *reinterpret_cast<const double*>(src + i * 4 + 2) + static_cast<double>(v.x);
             const float m = static_cast<float>(tot * inv_k64);

@@ -28,6 +28,12 @@ class Context:
         """mp_ctx_set_option: tuning knobs (results never depend on them)."""
         _lib.check(_lib.lib().mp_ctx_set_option(self.handle, key.encode(), int(value)))
 
+    def query(self, key: str) -> int:
+        """mp_ctx_query: diagnostics ("multi_staged_ranks")."""
+        v = C.c_uint64()
+        _lib.check(_lib.lib().mp_ctx_query(self.handle, key.encode(), C.byref(v)))
+        return v.value
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.lib().mp_ctx_destroy(self.handle)
