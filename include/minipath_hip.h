@@ -378,6 +378,37 @@ typedef struct {
 int mp_render_tiles_device_ex(mp_ctx *ctx, const mp_scene *scene, const mp_camera_sampler *sampler,
                               const mp_settings *settings, const mp_block *tiles, size_t n_tiles, float *d_rgba_f32,
                               const mp_launch_extras *extras, void *stream);
+/* First-hit feature planes.  BUILD-DEFINED (the reference's renderer reads only HitRecord.normal; denoisers, picking and
+ * compositing want the rest of the primary hit's HitRecord, geometry/mod.rs:71-80).  ONE launch traces the camera rays of the
+ * tiles once, on the packet walk, and writes up to four planes; each is tile-major, 4 dwords per pixel, laid out exactly like
+ * d_rgba_f32 of mp_render_tiles_device, and any may be NULL (a plane not asked for costs nothing).
+ * Rays: sample s of pixel (x, y) is the ray every render of the same mp_settings shoots first (sample_ray on the stream keyed by
+ * seed, width, sample_count, x, y, s).  MP_FLAG_PATHS and max_depth are accepted and ignored, so the settings of the beauty render
+ * give the planes of its primary hits.
+ * One rule for every float channel, the reference's own (worker.rs:40-44): acc = +0.0; for s = 0 .. sample_count-1 in index order
+ * acc = acc + (hit ? value : +0.0); pixel = acc * (1.0f / (float)sample_count).  The planes are coverage-weighted like the
+ * reference's rgb; alpha (hit count * the same factor) is there to divide by.
+ *   d_shade  : value = |d . n| -- the same bits as mp_render_tiles_device for the reference semantics.
+ *   d_normal : HitRecord.normal as mp_trace_rays reports it (not flipped towards the camera, not re-normalised after averaging),
+ *              and w = t of the world ray.
+ *   d_albedo : the reflectance the path extension multiplies the throughput by at this hit: mp_material.albedo of
+ *              HitRecord.material, or albedo2 on the odd cells of a MP_TEXTURE_CHECKER material (a NaN cell counts as odd; a
+ *              Sphere's texture coordinates are the origin; a Sphere scene, which has no table, has the default grey 0.75).
+ *   d_ids    : NOT averaged: the record of sample index 0 -- prim (MP_NO_PRIM on a miss), instance (member index, 0 outside object
+ *              groups), material (0 on a miss), 1 / 0 for hit / miss.  mp_untile scatters it like any other plane (it moves the
+ *              16-byte pixels' bit patterns untouched).
+ * Every scene kind mp_render_tiles_device renders.  MP_FLAG_ACCUMULATE, MP_FLAG_CHUNKED_SUM, MP_FLAG_WAVEFRONT and
+ * MP_FLAG_TRAVERSAL_GROUPS: MP_ERR_UNSUPPORTED.  All planes NULL, or n_tiles == 0: a no-op returning MP_OK.  `extras` (nullable):
+ * tile_order and d_tile_cost as in mp_render_tiles_device_ex; *d_ray_segments receives pixels * sample_count. */
+typedef struct {
+    float    *d_shade;      /* {c, c, c, alpha}: the reference's pixel (worker.rs:40-44, :59-65)     */
+    float    *d_normal;     /* {n.x, n.y, n.z, t}: HitRecord.normal (unflipped) and the hit distance */
+    float    *d_albedo;     /* {r, g, b, alpha}: reflectance of the primary hit's material           */
+    uint32_t *d_ids;        /* {prim, instance, material, hit ? 1 : 0} of sample 0 of the pixel      */
+} mp_aov_planes;
+int mp_render_aov_device(mp_ctx *ctx, const mp_scene *scene, const mp_camera_sampler *sampler, const mp_settings *settings,
+                         const mp_block *tiles, size_t n_tiles, const mp_aov_planes *planes, const mp_launch_extras *extras,
+                         void *stream);
 /* machinery.rs:78-89 (tile buffer -> image copy) on the device: scatters tile-major tiles into an image-major
  * f32 frame and/or its color_to_image u8 frame (either may be NULL). */
 int mp_untile(mp_ctx *ctx, const mp_settings *settings, const mp_block *tiles, size_t n_tiles,

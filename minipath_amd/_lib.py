@@ -173,6 +173,12 @@ class LaunchExtras(C.Structure):
     _fields_ = [("d_ray_segments", C.c_void_p), ("d_tile_cost", C.c_void_p), ("tile_order", C.POINTER(C.c_uint32))]
 
 
+class AovPlanes(C.Structure):
+    """mp_aov_planes: tile-major device planes of mp_render_aov_device, 16 bytes per pixel each; any may be NULL."""
+
+    _fields_ = [("d_shade", C.c_void_p), ("d_normal", C.c_void_p), ("d_albedo", C.c_void_p), ("d_ids", C.c_void_p)]
+
+
 STARTED_CB = C.CFUNCTYPE(None, C.c_void_p, Block)
 FINISHED_CB = C.CFUNCTYPE(None, C.c_void_p, Block, Progress)
 
@@ -237,6 +243,11 @@ SIGNATURES = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.POINTER(SamplerStruct), C.POINTER(SettingsStruct), C.POINTER(Block), C.c_size_t,
          C.c_void_p, C.POINTER(LaunchExtras), C.c_void_p],
+    ),
+    "mp_render_aov_device": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(SamplerStruct), C.POINTER(SettingsStruct), C.POINTER(Block), C.c_size_t,
+         C.POINTER(AovPlanes), C.POINTER(LaunchExtras), C.c_void_p],
     ),
     "mp_untile": (
         C.c_int,

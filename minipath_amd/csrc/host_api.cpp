@@ -1154,6 +1154,81 @@ int mp_render_tiles_device_ex(mp_ctx* ctx, const mp_scene* scene, const mp_camer
     });
 }
 
+// First-hit feature planes (build-defined, include/minipath_hip.h): validation as mp_render_tiles_device_ex, one launch.
+int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* sampler, const mp_settings* settings,
+                         const mp_block* tiles, size_t n_tiles, const mp_aov_planes* planes, const mp_launch_extras* extras,
+                         void* stream) {
+    return guarded([&]() -> int {
+    if (!ctx || !scene || !sampler || !planes || !settings) return fail(MP_ERR_INVALID, "bad argument");
+    if (settings->flags & (MP_FLAG_ACCUMULATE | MP_FLAG_CHUNKED_SUM))
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes are written by one launch over all samples: MP_FLAG_ACCUMULATE / MP_FLAG_CHUNKED_SUM are not supported");
+    if (settings->flags & (MP_FLAG_WAVEFRONT | MP_FLAG_TRAVERSAL_GROUPS))
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes run on the packet walk: MP_FLAG_WAVEFRONT / MP_FLAG_TRAVERSAL_GROUPS are not supported");
+    if (!valid_settings(settings)) return fail(MP_ERR_INVALID, "bad argument");
+    if (n_tiles && !tiles) return fail(MP_ERR_INVALID, "NULL tiles");
+    if (scene->ctx != ctx) return fail(MP_ERR_INVALID, "scene belongs to another context");
+    if (n_tiles == 0 || !(planes->d_shade || planes->d_normal || planes->d_albedo || planes->d_ids)) return MP_OK;
+    if (n_tiles > 0xFFFFFFFFull) return fail(MP_ERR_INVALID, "too many tiles");
+    uint64_t* d_ray_segments = extras ? extras->d_ray_segments : nullptr;
+    const uint32_t* tile_order = extras ? extras->tile_order : nullptr;
+    uint64_t rays = 0;
+    for (size_t i = 0; i < n_tiles; i++) {
+        const mp_block& t = tiles[i];
+        if (!(t.min_x < t.max_x && t.min_y < t.max_y) || t.max_x - t.min_x > settings->tile_size ||
+            t.max_y - t.min_y > settings->tile_size || t.max_x > settings->width || t.max_y > settings->height)
+            return fail(MP_ERR_INVALID, "tile empty, larger than tile_size, or outside the resolution");
+        rays += static_cast<uint64_t>(t.max_x - t.min_x) * (t.max_y - t.min_y) * settings->sample_count;
+    }
+    if (tile_order) {  // must be a permutation: every tile is rendered exactly once
+        std::vector<bool> seen(n_tiles, false);
+        for (size_t i = 0; i < n_tiles; i++) {
+            if (tile_order[i] >= n_tiles || seen[tile_order[i]]) return fail(MP_ERR_INVALID, "tile_order is not a permutation of 0..n_tiles-1");
+            seen[tile_order[i]] = true;
+        }
+    }
+    DeviceGuard g(ctx->device);
+    const mp_block* d_tiles = nullptr;
+    const uint32_t* d_order = nullptr;
+    mp_ctx::TileListRef keep;  // held until the launch below is enqueued
+    int rc = ctx->device_tiles(tiles, n_tiles, tile_order, keep, &d_tiles, &d_order);
+    if (rc) return rc;
+    std::string err;
+    if (d_ray_segments) {  // one Object::intersect per sample
+        rc = launch_set_u64(reinterpret_cast<unsigned long long*>(d_ray_segments), rays, stream, err);
+        if (rc) return fail(rc, err);
+    }
+    RenderLaunch L;
+    L.scene = scene->dev;
+    L.scene.packet_stack_regs = ctx->packet_stack_regs.load();
+    L.packet_samples = ctx->packet_samples.load();
+    L.mask_cache = ctx->mask_cache.load();
+    L.sampler = *sampler;
+    L.width = settings->width;
+    L.height = settings->height;
+    L.spp = settings->sample_count;
+    L.tile_size = settings->tile_size;
+    L.seed = settings->seed;
+    L.d_tiles = d_tiles;
+    L.n_tiles = static_cast<uint32_t>(n_tiles);
+    L.d_out = nullptr;
+    L.d_counter = ctx->take_counter();
+    {
+        const uint32_t bpc = ctx->blocks_per_cu.load();
+        L.cu_count = bpc ? std::max(1, ctx->cu_count * static_cast<int>(bpc) / 8) : ctx->cu_count;
+    }
+    L.traversal = 0;
+    L.max_depth = 0;  // MP_FLAG_PATHS / max_depth: accepted and ignored
+    L.d_segments = nullptr;
+    L.d_tile_order = d_order;
+    L.d_tile_cost = reinterpret_cast<unsigned long long*>(extras ? extras->d_tile_cost : nullptr);
+    L.pass_begin = 0;
+    L.pass_end = settings->sample_count;
+    rc = launch_render_aov(L, *planes, stream, err);
+    if (rc) return fail(rc, err);
+    return MP_OK;
+    });
+}
+
 int mp_untile(mp_ctx* ctx, const mp_settings* settings, const mp_block* tiles, size_t n_tiles, const float* d_tiles_f32,
               float* d_image_f32, uint8_t* d_image_u8, void* stream) {
     return guarded([&]() -> int {

@@ -1723,6 +1723,171 @@ __device__ __forceinline__ void pixel_state_store3(const RenderParams& P, size_t
     *reinterpret_cast<float4*>(P.out + off) = make_float4(acc[0] * s, acc[1] * s, acc[2] * s, cnt * s);
 }
 
+// ---- build-defined first-hit feature planes (mp_render_aov_device, include/minipath_hip.h) ----------------------------------
+struct AovParams {
+    RenderParams r;   // r.out is not used
+    float* shade;     // {c, c, c, alpha}
+    float* normal;    // {n.x, n.y, n.z, t}
+    float* albedo;    // {r, g, b, alpha}
+    uint32_t* ids;    // {prim, instance, material, hit} of sample 0
+};
+
+// Reflectance of a hit: the factor path_vertex multiplies the throughput by (mp_material.albedo, or albedo2 on the odd cells of a
+// MP_TEXTURE_CHECKER material; NaN cells count as odd; a Sphere's texture coordinates are the origin).  RESTATED from path_vertex,
+// not shared with it: path_vertex's instantiations stay exactly as measured, and tests/test_gpu_aov.py holds the two rules together
+// (its checker case compares this kernel with a model of path_vertex's rule).  A scene without a material table (Scene<Sphere>)
+// has the default material.
+template <bool OBJ>
+__device__ __forceinline__ void hit_albedo(const DevScene& sc, uint32_t inst, uint32_t mat, uint32_t prim, float u, float v, float (&a)[3]) {
+    if (sc.materials == nullptr) { a[0] = a[1] = a[2] = 0.75f; return; }
+    const float* m = sc.materials + static_cast<size_t>(mat) * 12;
+    const float* alb = m;
+    if (as_u(m[9]) == MP_TEXTURE_CHECKER) {
+        float tx = 0.0f, ty = 0.0f;
+        if (OBJ) {
+            DevScene so;
+            object_scene(sc, inst, so);
+            if (so.kind == 0u) hit_tex(so, prim, u, v, tx, ty);
+        } else {
+            hit_tex(sc, prim, u, v, tx, ty);
+        }
+        const float cell = floorf(tx * m[10]) + floorf(ty * m[10]);
+        const float half = cell * 0.5f;
+        if (half - floorf(half) != 0.0f) alb = m + 6;
+    }
+    a[0] = alb[0]; a[1] = alb[1]; a[2] = alb[2];
+}
+
+// The packet render with up to four planes per pixel.  Work units, queues, ray generation, pre-test and walk are those of
+// render_tiles_packet_kernel (called, not copied); new is what follows the walk: normal, material and texture cell per lane, then
+// up to eight channels through add_samples_in_order and the id record of the lane that holds sample 0.
+// Registers: the eight running sums of a pixel do NOT live across the walk.  Every lane of a pixel ends a pass with the same sums,
+// so the pixel's first lane parks them in LDS (8 dwords per pixel, 64/S pixels per wave: 32 B .. 2 KB per wave, in front of the
+// mask cache / the LDS stack) and every lane of the pixel reads them back (a broadcast read) for the adds of the next pass; only
+// the hit count stays in a register, as in the render kernel.  Planes the caller did not ask for are skipped by wave-uniform
+// branches on the plane pointers (scalar loads from the kernel arguments): a compile-time plane mask would multiply the
+// instantiations by up to 15 for the price of a few s_cbranch per pass.
+template <int S, bool LDS_STACK, int WPE, bool OBJ = false, bool MCACHE = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void render_aov_packet_kernel(AovParams) {
+    extern __shared__ __align__(16) unsigned char smem[];
+    typedef const __attribute__((address_space(4))) AovParams* kaov_t;
+    kaov_t KP = (kaov_t)__builtin_amdgcn_kernarg_segment_ptr();
+    constexpr int BW = (S <= 2) ? 8 : (S <= 8) ? 4 : (S <= 32) ? 2 : 1;  // pixel block = BW x BH, BW*BH*S == 64
+    constexpr int BH = 64 / S / BW;
+    constexpr uint32_t kParkWave = (64 / S) * 32;  // bytes of parked sums per wave
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    const int pix = lane / S, sub = lane % S;
+    uint32_t qstate = blockIdx.x % kWorkQueues;
+    MaskCache mc{nullptr};
+    if (MCACHE) mc.lds = reinterpret_cast<uint32_t*>(smem + 4 * kParkWave) + static_cast<size_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6)) * kMaskCacheDwords;
+    for (;;) {
+        const RenderParams& P = kernarg_view<AovParams>(KP).r;  // unit setup
+        const uint32_t ts = P.tile_size;
+        const uint32_t bx = (ts + BW - 1) / BW, by = (ts + BH - 1) / BH, upt = bx * by, total = P.n_tiles * upt;
+        MP_NEXT_UNIT(unit)
+        const uint32_t b = unit % upt;
+        const uint32_t tile_i = P.tile_order ? P.tile_order[unit / upt] : unit / upt;
+        const uint64_t t_unit = P.tile_cost ? __builtin_readcyclecounter() : 0;
+        const mp_block T = P.tiles[tile_i];
+        const uint32_t px = T.min_x + (b % bx) * BW + static_cast<uint32_t>(pix % BW);
+        const uint32_t py = T.min_y + (b / bx) * BH + static_cast<uint32_t>(pix / BW);
+        const bool inpix = px < T.max_x && py < T.max_y;
+        if (__ballot(inpix) == 0) continue;
+        const size_t off = (static_cast<size_t>(tile_i) * ts * ts + static_cast<size_t>(py - T.min_y) * ts + (px - T.min_x)) * 4;
+        float cnt = 0.0f;  // alpha (worker.rs:40)
+        {
+            float4* park = reinterpret_cast<float4*>(smem + static_cast<size_t>(static_cast<int>(threadIdx.x) >> 6) * kParkWave) + pix * 2;
+            if (sub == 0) park[0] = park[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (MCACHE && lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;  // a new unit: other pixels, other bounds
+            wave_lds_sync();
+        }
+        const uint32_t s_end = P.s_end;
+        for (uint32_t s0 = 0; s0 < s_end; s0 += S) {
+            const uint32_t s = s0 + static_cast<uint32_t>(sub);
+            const bool act = inpix && s < s_end;
+            Ray r;
+            r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
+            {
+                const RenderParams& G = kernarg_view<AovParams>(KP).r;  // ray generation
+                if (act) sample_ray(G.gen, px, py, s, r);
+            }
+            PacketHit h;
+            h.t = FLT_MAX; h.u = h.v = 0.0f; h.prim = kNoPrim;
+            uint32_t hinst = 0u;
+            {
+                const RenderParams& W = kernarg_view<AovParams>(KP).r;  // walk
+                float* lds = reinterpret_cast<float*>(smem + 4 * kParkWave + static_cast<size_t>(static_cast<int>(threadIdx.x) >> 6) * W.lds_per_wave);
+                if (OBJ) {
+                    if (LDS_STACK) {
+                        HybridStack st(lds, lane, W.scene.stack_cap, W.scene.packet_stack_regs);
+                        trace_packet_objects<false>(W.scene, r, act, st, h, hinst);
+                    } else {
+                        RegStack st(lds, lane);
+                        trace_packet_objects<(S == 16)>(W.scene, r, act, st, h, hinst);
+                    }
+                } else {
+                    const bool go = act && W.scene.kind == 0u && may_hit_scene(W.scene, r);
+                    if (__ballot(go) != 0) {
+                        if (LDS_STACK) {
+                            HybridStack st(lds, lane, W.scene.stack_cap, W.scene.packet_stack_regs);
+                            trace_packet<false>(W.scene, r, go, st, h);
+                        } else {
+                            RegStack st(lds, lane);
+                            trace_packet<(S == 16 || MCACHE), RegStack, MCACHE>(W.scene, r, go, st, h, mc);
+                        }
+                    }
+                }
+            }
+            const AovParams& H = kernarg_view<AovParams>(KP);  // hit record + accumulation
+            bool hit = h.prim != kNoPrim;
+            float nn[3] = {0.0f, 0.0f, 0.0f};
+            uint32_t mat = 0u;
+            if (hit) {
+                mat = OBJ ? object_normal(H.r.scene, hinst, r, h.prim, h.u, h.v, nn) : resolve_normal(H.r.scene, h.prim, h.u, h.v, nn);
+            } else if (H.r.scene.kind == 1u) {  // Scene<Sphere>: prim 0, material 0 (primitives.rs:40-46)
+                hit = act && sphere_intersect(H.r.scene, r, h.t, nn);
+                if (hit) h.prim = 0u;
+            }
+            if (H.ids && inpix && s == 0u)  // not averaged: the record of sample 0
+                *reinterpret_cast<uint4*>(H.ids + off) = hit ? make_uint4(h.prim, hinst, mat, 1u) : make_uint4(kNoPrim, 0u, 0u, 0u);
+            int l_ = lane;  // (pixel mask and park address rebuilt from the lane id here: nothing of them lives across the walk)
+            asm volatile("" : "+v"(l_));
+            const uint64_t pixel_lanes = (S == 64 ? ~0ull : ((1ull << (S & 63)) - 1ull)) << (l_ & ~(S - 1));
+            cnt += static_cast<float>(__popcll(__ballot(hit) & pixel_lanes));  // exact integers: the order is irrelevant
+            float4* park = reinterpret_cast<float4*>(smem + static_cast<size_t>(static_cast<int>(threadIdx.x) >> 6) * kParkWave) + (l_ / S) * 2;
+            float4 a0 = park[0], a1 = park[1];  // {shade, n.x, n.y, n.z}, {t, r, g, b}
+            // misses add +0.0 (exact)
+            if (H.shade) add_samples_in_order<S>(a0.x, hit ? fabsf(r.dx * nn[0] + r.dy * nn[1] + r.dz * nn[2]) : 0.0f, lane);  // worker.rs:60
+            if (H.normal) {
+                add_samples_in_order<S>(a0.y, hit ? nn[0] : 0.0f, lane);
+                add_samples_in_order<S>(a0.z, hit ? nn[1] : 0.0f, lane);
+                add_samples_in_order<S>(a0.w, hit ? nn[2] : 0.0f, lane);
+                add_samples_in_order<S>(a1.x, hit ? h.t : 0.0f, lane);
+            }
+            if (H.albedo) {
+                float al[3] = {0.0f, 0.0f, 0.0f};
+                if (hit) hit_albedo<OBJ>(H.r.scene, hinst, mat, h.prim, h.u, h.v, al);
+                add_samples_in_order<S>(a1.y, al[0], lane);
+                add_samples_in_order<S>(a1.z, al[1], lane);
+                add_samples_in_order<S>(a1.w, al[2], lane);
+            }
+            wave_lds_sync();  // every lane of the pixel has read the old sums
+            if ((l_ & (S - 1)) == 0) { park[0] = a0; park[1] = a1; }
+            wave_lds_sync();
+        }
+        const AovParams& E = kernarg_view<AovParams>(KP);  // unit end: pixel = sum * inv_spp (worker.rs:44)
+        if (inpix && sub == 0) {
+            const float4* park = reinterpret_cast<const float4*>(smem + static_cast<size_t>(static_cast<int>(threadIdx.x) >> 6) * kParkWave) + pix * 2;
+            const float4 a0 = park[0], a1 = park[1];
+            const float inv = E.r.inv_spp, a = cnt * inv;
+            if (E.shade) { const float m = a0.x * inv; *reinterpret_cast<float4*>(E.shade + off) = make_float4(m, m, m, a); }
+            if (E.normal) *reinterpret_cast<float4*>(E.normal + off) = make_float4(a0.y * inv, a0.z * inv, a0.w * inv, a1.x * inv);
+            if (E.albedo) *reinterpret_cast<float4*>(E.albedo + off) = make_float4(a1.y * inv, a1.z * inv, a1.w * inv, a);
+        }
+        if (E.r.tile_cost && lane == 0) atomicAdd(E.r.tile_cost + tile_i, static_cast<unsigned long long>(__builtin_readcyclecounter() - t_unit));
+    }
+}
+
 #ifndef MP_PATHS_WPE
 #define MP_PATHS_WPE 6  // waves per SIMD the path kernel's registers are held to (A/B-measured, profiles/r03_notes.md)
 #endif
@@ -2831,6 +2996,80 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
     else MP_LAUNCH_PACKET(1, 7);
 #undef MP_LAUNCH_PACKET
     return check(hipGetLastError(), "render_tiles_packet_kernel launch", err);
+}
+
+// mp_render_aov_device: the packet kernel with feature planes (render_aov_packet_kernel).  Samples in flight and mask cache follow
+// launch_render_tiles' rules on a shorter list of instantiations: S = 16 from 16 samples per pixel on, 4 from 4 on, else 1;
+// with the mask cache (same conditions: stack in registers, no object group, units of at least four passes) 16 from 64 samples on
+// and 4 for 16-63; object groups and LDS-stack scenes 16 or 1.  A packet_samples_in_flight request is rounded down to these.
+int launch_render_aov(const RenderLaunch& L, const mp_aov_planes& planes, void* stream, std::string& err) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (L.n_tiles == 0) return MP_OK;
+    AovParams A;
+    RenderParams& P = A.r;
+    P.scene = L.scene;
+    P.gen.s = L.sampler;
+    P.gen.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
+    P.gen.width = L.width;
+    P.gen.spp = L.spp;
+    P.gen.seed = mixed_seed(L.seed);
+    P.tiles = L.d_tiles;
+    P.n_tiles = L.n_tiles;
+    P.tile_size = L.tile_size;
+    P.out = nullptr;
+    P.counter = L.d_counter;
+    P.inv_spp = 1.0f / static_cast<float>(L.spp);
+    P.s_begin = 0;
+    P.s_end = L.spp;
+    P.carry_in = 0u;
+    P.finalize = 1u;
+    P.chunked = 0u;
+    P.tile_order = L.d_tile_order;
+    P.tile_cost = L.d_tile_cost;
+    P.max_depth = 0;
+    P.segments = nullptr;
+    P.pool = nullptr;
+    P.pool_stride = 0;
+    A.shade = planes.d_shade;
+    A.normal = planes.d_normal;
+    A.albedo = planes.d_albedo;
+    A.ids = planes.d_ids;
+    int rc = check(hipMemsetAsync(L.d_counter, 0, kWorkQueues * kWorkQueueStride * sizeof(uint32_t), st), "hipMemsetAsync(counter)", err);
+    if (rc) return rc;
+    const uint64_t units = static_cast<uint64_t>(L.n_tiles) * ((L.tile_size + 7) / 8) * ((L.tile_size + 7) / 8);
+    const uint64_t want = (units + 3) / 4;
+    const uint32_t nspp = L.spp;
+    const bool obj = L.scene.inst_count != 0u;
+    const bool lds_stack = L.scene.stack_cap > L.scene.packet_stack_regs;
+    int S = nspp >= 16 ? 16 : nspp >= 4 ? 4 : 1;
+    const bool cache_ok = L.mask_cache != 0u && !lds_stack && !obj && L.scene.kind == 0u && L.scene.inner_count < (1u << 24) && L.scene.tris_bounded != 0u;
+    if (cache_ok && nspp >= 16) S = nspp >= 64 ? 16 : 4;
+    if (L.packet_samples) S = L.packet_samples >= 16u ? 16 : L.packet_samples >= 4u ? 4 : 1;
+    if ((obj || lds_stack) && S == 4) S = 1;
+    const bool mcache = cache_ok && S >= 4 && nspp >= 4u * static_cast<uint32_t>(S);
+    P.lds_per_wave = lds_stack ? (L.scene.stack_cap - L.scene.packet_stack_regs) * 16u : 0u;
+    const uint32_t park = 4u * (64u / static_cast<uint32_t>(S)) * 32u;  // the parked sums of the block's four waves
+    const uint32_t lds = park + (mcache ? 4u * kMaskCacheDwords * 4u : P.lds_per_wave * 4u);
+    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stack"; return MP_ERR_UNSUPPORTED; }
+    const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / lds));
+    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
+#define MP_LAUNCH_AOV(...) hipLaunchKernelGGL((render_aov_packet_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds, st, A)
+    if (mcache) {
+        if (S == 16) MP_LAUNCH_AOV(16, false, 8, false, true);
+        else MP_LAUNCH_AOV(4, false, 8, false, true);
+    } else if (obj) {
+        if (S == 16 && lds_stack) MP_LAUNCH_AOV(16, true, 6, true);
+        else if (S == 16) MP_LAUNCH_AOV(16, false, 6, true);
+        else if (lds_stack) MP_LAUNCH_AOV(1, true, 6, true);
+        else MP_LAUNCH_AOV(1, false, 6, true);
+    } else if (lds_stack) {
+        if (S == 16) MP_LAUNCH_AOV(16, true, 8);
+        else MP_LAUNCH_AOV(1, true, 8);
+    } else if (S == 16) MP_LAUNCH_AOV(16, false, 8);
+    else if (S == 4) MP_LAUNCH_AOV(4, false, 8);
+    else MP_LAUNCH_AOV(1, false, 8);
+#undef MP_LAUNCH_AOV
+    return check(hipGetLastError(), "render_aov_packet_kernel launch", err);
 }
 
 int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::string& err) {

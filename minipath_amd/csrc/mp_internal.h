@@ -181,6 +181,8 @@ struct RenderLaunch {
 
 int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err);
 int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::string& err);
+// mp_render_aov_device: the packet render with feature planes (L.d_out, the pass range and the path fields are not read)
+int launch_render_aov(const RenderLaunch& L, const mp_aov_planes& planes, void* stream, std::string& err);
 int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx,
                       const float* dy, const float* dz, uint64_t n, const mp_hits_soa& hits, int cu_count, void* stream,
                       std::string& err);

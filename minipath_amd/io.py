@@ -72,7 +72,11 @@ def save_exr(path: str, rgba_f32: np.ndarray) -> None:
     h, w, nc = img.shape
     names = ["A", "B", "G", "R"] if nc == 4 else ["B", "G", "R"]  # channels are stored in alphabetical order
     plane = {"R": 0, "G": 1, "B": 2, "A": 3}
+    _write_exr(path, w, h, names, [img[:, :, plane[n]] for n in names])
 
+
+def _write_exr(path: str, w: int, h: int, names, planes) -> None:
+    """Uncompressed FLOAT scanline file: channel names[k] (already in the order EXR requires) = planes[k], [h, w] '<f4'."""
     def attr(name: str, typ: str, value: bytes) -> bytes:
         return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(value)) + value
 
@@ -95,13 +99,45 @@ def save_exr(path: str, rgba_f32: np.ndarray) -> None:
         f.write(np.arange(h, dtype="<u8").__mul__(row_bytes).__add__(first).tobytes())  # scanline offset table
         for y in range(h):
             f.write(struct.pack("<ii", y, len(names) * w * 4))
-            for n in names:
-                f.write(img[y, :, plane[n]].tobytes())
+            for p in planes:
+                f.write(p[y].tobytes())
 
 
-def load_exr_f32(path: str) -> np.ndarray:
-    """Reader for the files save_exr writes (uncompressed FLOAT scanlines): round-trip tests.  Returns [h, w, channels] in
-    R, G, B(, A) order."""
+def save_exr_layers(path: str, layers: dict) -> None:
+    """Write named float planes (the feature planes of FrameRenderer.render_aov beside a beauty image) into ONE uncompressed
+    32-bit-float scanline OpenEXR file.  `layers` maps a name to an [h, w] array (one channel of that name) or an [h, w, k] array
+    with k <= 4 (channels name.R, name.G, name.B, name.A -- or name.X, name.Y, name.Z for the names "N" and "normal"); all of
+    one size.  Channels are stored sorted by name (byte order), as EXR requires; the values survive bit for bit.  Example:
+    save_exr_layers(p, {"N": nxyz, "Z": t, "albedo": rgb, "A": alpha}); load_exr_f32(p, layers=True) reads it back."""
+    chans = {}
+    for name, arr in layers.items():
+        a = np.asarray(arr)
+        if a.dtype != np.float32:
+            raise ValueError(f"layer {name!r}: expected float32")
+        if a.ndim == 2:
+            chans[str(name)] = a
+        elif a.ndim == 3 and 1 <= a.shape[2] <= 4:
+            suffix = "XYZW" if str(name) in ("N", "normal") else "RGBA"
+            for k in range(a.shape[2]):
+                chans[f"{name}.{suffix[k]}"] = a[:, :, k]
+        else:
+            raise ValueError(f"layer {name!r}: expected [h, w] or [h, w, k <= 4]")
+    if not chans:
+        raise ValueError("no layers")
+    shapes = {c.shape for c in chans.values()}
+    if len(shapes) != 1:
+        raise ValueError("layers differ in size")
+    for n in chans:
+        if not n or len(n.encode()) > 255 or "\0" in n:
+            raise ValueError(f"bad channel name {n!r}")
+    (h, w), = shapes
+    names = sorted(chans, key=lambda n: n.encode())
+    _write_exr(path, w, h, names, [np.ascontiguousarray(chans[n], dtype="<f4") for n in names])
+
+
+def load_exr_f32(path: str, layers: bool = False):
+    """Reader for the files save_exr / save_exr_layers write (uncompressed FLOAT scanlines): round-trip tests.  Returns
+    [h, w, channels] in R, G, B(, A) order; layers=True: (channel names in file order, {channel name: [h, w] array})."""
     data = open(path, "rb").read()
     if struct.unpack("<i", data[:4])[0] != 20000630:
         raise ValueError("not an OpenEXR file")
@@ -124,6 +160,13 @@ def load_exr_f32(path: str) -> np.ndarray:
             raise ValueError("only FLOAT channels")
         q = e + 17
     offs = np.frombuffer(data, "<u8", h, pos)
+    if layers:
+        planes = {n: np.zeros((h, w), np.float32) for n in names}
+        for y in range(h):
+            o = int(offs[y]) + 8
+            for k, n in enumerate(names):
+                planes[n][y] = np.frombuffer(data, "<f4", w, o + k * w * 4)
+        return names, planes
     out = np.zeros((h, w, len(names)), np.float32)
     order = {"R": 0, "G": 1, "B": 2, "A": 3}
     for y in range(h):

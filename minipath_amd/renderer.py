@@ -307,6 +307,40 @@ class FrameRenderer:
         )
         return self.tile_buf
 
+    def render_aov(self, shade: bool = True, normal: bool = True, albedo: bool = True, ids: bool = True) -> dict:
+        """First-hit feature planes of this renderer's tiles in ONE launch (mp_render_aov_device); asynchronous on the current
+        stream.  Returns a dict of new tile-major tensors shaped like `tile_buf`: "shade" {c, c, c, alpha}, "normal"
+        {n.x, n.y, n.z, t}, "albedo" {r, g, b, alpha} (float32; sums over the samples * 1/spp, i.e. coverage-weighted: divide by
+        alpha where it is not 0) and "ids" {prim, instance, material, hit} of sample 0 (int32; prim -1 = MP_NO_PRIM on a miss).
+        Planes not asked for are not computed.  MP_FLAG_PATHS in the settings is ignored: the planes are those of the beauty
+        render's primary hits.  untile_plane() scatters a plane into an image."""
+        import torch
+
+        ts = self.settings.tile_size
+        shape = (max(len(self.tiles), 1), ts, ts, 4)
+        out = {}
+        for name, want, dt in (("shade", shade, torch.float32), ("normal", normal, torch.float32), ("albedo", albedo, torch.float32),
+                               ("ids", ids, torch.int32)):
+            if want:
+                out[name] = torch.zeros(shape, dtype=dt, device=self.device)
+        planes = _lib.AovPlanes(*[out[k].data_ptr() if k in out else None for k in ("shade", "normal", "albedo", "ids")])
+        _lib.check(
+            _lib.lib().mp_render_aov_device(
+                self.ctx.handle, self.scene.object.handle, C.byref(self._sampler), C.byref(self._st), self._tiles_c,
+                len(self.tiles), C.byref(planes), C.byref(self._extras), self._stream(),
+            )
+        )
+        return out
+
+    def untile_plane(self, plane):
+        """A tile-major plane of render_aov() -> image-major [h, w, 4] of the same dtype.  The scatter moves the 16-byte pixels'
+        bit patterns untouched, so the int32 "ids" plane goes through the float path as a view."""
+        import torch
+
+        if plane.dtype == torch.float32:
+            return self.untile(tile_buf=plane, want_u8=False)[0]
+        return self.untile(tile_buf=plane.view(torch.float32), want_u8=False)[0].view(plane.dtype)
+
     def rebalance(self) -> List[int]:
         """Order the following launches' tile hand-out by the measured cost of the launches so far (most expensive first), and
         reset the cost counters.  Synchronises the device (reads `tile_cost`).  The image does not depend on the order; the
