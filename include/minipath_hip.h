@@ -207,7 +207,9 @@ int mp_ctx_device(const mp_ctx *ctx, int *device_id, int *cu_count);
 /* Tuning knobs.  "packet_stack_registers" (1..64, default 64): entries of the ray-packet walk's shared stack kept in registers; the
  * rest of the scene's stack bound lives in LDS.  "packet_samples_in_flight" (0 = automatic, or 1, 2, 4, ... 64): samples of one pixel
  * a wavefront traces per pass (64 / value pixels side by side); sets the size of a work unit.  "packet_rays_per_lane" (1 default,
- * or 2): 2 = 128-ray walks, two rays per lane (measured slower on MI355X; kept as the measured alternative).  "blocks_per_cu"
+ * or 2): 2 = 128-ray walks, two rays per lane (measured slower on MI355X; kept as the measured alternative); it takes effect
+ * only where a launch has 16 samples in flight on a plain TriangleBvh whose stack fits the registers (ask for them with
+ * "packet_samples_in_flight": the automatic choice is 16 for few sample counts), and is ignored elsewhere.  "blocks_per_cu"
  * (0 = as many as fit, or 1..8): resident workgroups per CU, a diagnostic knob for occupancy studies.  "packet_mask_cache" (1
  * default): the packet walk's per-work-unit cache of "children / triangles no ray of the unit can hit" masks (exact: interval
  * evaluation of the reference's own tests on bounds of the unit's rays): 0 = off, 1 or 2 = on wherever a work unit has at least
@@ -223,6 +225,21 @@ int mp_ctx_set_option(mp_ctx *ctx, const char *key, int value);
 /* Diagnostics.  "multi_staged_ranks": ranks of the last frame gathered on ctx (as ctxs[0] of mp_render_frame_multi /
  * mp_render_pass_multi) whose shard travelled through pinned host memory. */
 int mp_ctx_query(mp_ctx *ctx, const char *key, uint64_t *value);
+/* Diagnostics.  The kernels launched by the last call on ctx that launched any (mp_render_tile, mp_render_tiles_device*,
+ * mp_render_aov_device, mp_untile*, mp_trace_rays*, mp_occluded_rays, mp_generate_rays; one call = one record, so mp_render_tile
+ * reports its render kernel only, and mp_render_tiles_device_ex with d_ray_segments the counter's set_u64_kernel before the render
+ * kernel): the kernels' names with their template arguments as the launcher writes them, e.g.
+ * "render_tiles_packet_kernel<16, false, 8, false, true>", distinct names in launch order, separated by '\n' (the staged path
+ * evaluation launches several kernels per bounce: each name once).  The record is made by the statement that launches, so a
+ * test can pin which instantiation an input selects; it is made before the launch, so a launch that the runtime refuses (the
+ * call then returns MP_ERR_HIP) is in the record too.  A call that launches nothing (refused, or no tiles) leaves the record as
+ * it was.  Copies at most cap - 1 characters and a terminating 0 to buf (nullable when cap is 0); *needed (nullable) = length
+ * of the whole text without the 0.  Thread-safe.  mp_render_begin: every batch of a worker thread (render kernel + the
+ * quantise_kernel of color_to_image) is one record, so while a render runs, and after it, the call reports the last batch that
+ * was enqueued on ctx; batches of one frame may differ in their kernels (the launchers look at the size of the launch).
+ * mp_render_frame_multi / mp_render_pass_multi: every rank's context reports its own render launch, and ctxs[0] after a gather
+ * the untile_kernel. */
+int mp_ctx_last_kernels(mp_ctx *ctx, char *buf, size_t cap, size_t *needed);
 
 /* ---- camera.rs ------------------------------------------------------------------------------------------ */
 int mp_camera_default(mp_camera *cam);                                                            /* :42-52 */

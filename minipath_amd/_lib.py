@@ -191,6 +191,7 @@ SIGNATURES = {
     "mp_ctx_destroy": (None, [C.c_void_p]),
     "mp_ctx_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "mp_ctx_query": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]),
+    "mp_ctx_last_kernels": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "mp_ctx_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "mp_camera_default": (C.c_int, [C.POINTER(CameraStruct)]),
     "mp_camera_look_at": (C.c_int, [C.POINTER(CameraStruct), _f3, _f3, _f3]),

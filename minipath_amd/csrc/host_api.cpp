@@ -151,6 +151,9 @@ struct mp_ctx {
         const mp_scene* acc_scene = nullptr;
     } multi;
     std::mutex multi_mu;
+    // mp_ctx_last_kernels: the kernels of the last launching call (LaunchScope)
+    std::mutex diag_mu;
+    std::string last_kernels;
     static constexpr size_t kTileLists = 32;
     std::mutex tile_mutex;
     std::vector<TileListRef> tile_lists;
@@ -485,6 +488,29 @@ uint32_t pass_samples(const mp_settings& st) {
     return st.pass_count ? st.pass_count : st.sample_count - st.pass_begin;
 }
 
+// One record of mp_ctx_last_kernels: the launchers note their kernels in a list of the calling thread (kernels.hip: MP_LAUNCH); the
+// outermost scope on a thread empties that list when it opens and, if anything was launched, files it with the context when it
+// closes.  Entry points nest (mp_render_tile calls mp_render_tiles_device): the inner scopes do nothing.
+struct LaunchScope {
+    static thread_local int depth;
+    mp_ctx* ctx;
+    explicit LaunchScope(mp_ctx* c) : ctx(c) {
+        if (depth++ == 0) launch_log_clear();
+    }
+    ~LaunchScope() {
+        if (--depth != 0 || !ctx) return;
+        try {
+            std::string names = launch_log_text();
+            if (names.empty()) return;
+            std::lock_guard<std::mutex> lk(ctx->diag_mu);
+            ctx->last_kernels.swap(names);
+        } catch (...) {}
+    }
+    LaunchScope(const LaunchScope&) = delete;
+    LaunchScope& operator=(const LaunchScope&) = delete;
+};
+thread_local int LaunchScope::depth = 0;
+
 // The refusals of render_tiles_device that the scene and the settings decide alone, before anything is launched (0 = none).
 int render_refusal(const mp_scene* scene, const mp_settings& st) {
     if ((st.flags & MP_FLAG_PATHS) && (st.flags & MP_FLAG_CHUNKED_SUM) && scene->dev.materials_rgb)
@@ -641,6 +667,20 @@ int mp_ctx_query(mp_ctx* ctx, const char* key, uint64_t* value) {
         return MP_OK;
     }
     return fail(MP_ERR_INVALID, std::string("unknown query: ") + key);
+    });
+}
+
+int mp_ctx_last_kernels(mp_ctx* ctx, char* buf, size_t cap, size_t* needed) {
+    return guarded([&]() -> int {
+    if (!ctx || (cap && !buf)) return fail(MP_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ctx->diag_mu);
+    if (needed) *needed = ctx->last_kernels.size();
+    if (cap) {
+        const size_t n = std::min(cap - 1, ctx->last_kernels.size());
+        std::memcpy(buf, ctx->last_kernels.data(), n);
+        buf[n] = 0;
+    }
+    return MP_OK;
     });
 }
 
@@ -1031,6 +1071,7 @@ int mp_trace_rays(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, const f
     if (n && (!d_ox || !d_oy || !d_oz || !d_dx || !d_dy || !d_dz)) return fail(MP_ERR_INVALID, "NULL ray array");
     if (scene->ctx != ctx) return fail(MP_ERR_INVALID, "scene belongs to another context");
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     std::string err;
     const uint32_t bpc = ctx->blocks_per_cu.load();
     int rc = launch_trace_rays(scene->dev, d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, n, *hits, ctx->cu_count * (bpc ? static_cast<int>(bpc) : 8) / 8, stream, err);
@@ -1044,6 +1085,7 @@ static int query_rays(mp_ctx* ctx, const mp_scene* scene, const float* d_ox, con
                       const float* d_dx, const float* d_dy, const float* d_dz, const float* d_tmax, uint64_t n,
                       const mp_hits_soa* hits, uint8_t* d_occluded, void* stream) {
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     std::string err;
     const uint32_t bpc = ctx->blocks_per_cu.load();
     int rc = launch_query_rays(scene->dev, d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax, n, hits, d_occluded,
@@ -1083,6 +1125,7 @@ int mp_generate_rays(mp_ctx* ctx, const mp_camera_sampler* sampler, const mp_set
     if (!(block.min_x <= block.max_x && block.min_y <= block.max_y)) return fail(MP_ERR_INVALID, "inverted block");
     if (!d_ox || !d_oy || !d_oz || !d_dx || !d_dy || !d_dz) return fail(MP_ERR_INVALID, "NULL ray array");
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     std::string err;
     int rc = launch_generate_rays(*sampler, settings->width, settings->sample_count, settings->seed, block, sample, d_ox,
                                   d_oy, d_oz, d_dx, d_dy, d_dz, stream, err);
@@ -1135,6 +1178,7 @@ int mp_render_tiles_device_ex(mp_ctx* ctx, const mp_scene* scene, const mp_camer
         }
     }
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     const mp_block* d_tiles = nullptr;
     const uint32_t* d_order = nullptr;
     mp_ctx::TileListRef keep;  // held until the launch below is enqueued
@@ -1187,6 +1231,7 @@ int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sam
         }
     }
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     const mp_block* d_tiles = nullptr;
     const uint32_t* d_order = nullptr;
     mp_ctx::TileListRef keep;  // held until the launch below is enqueued
@@ -1237,6 +1282,7 @@ int mp_untile(mp_ctx* ctx, const mp_settings* settings, const mp_block* tiles, s
     if (!tiles || !d_tiles_f32) return fail(MP_ERR_INVALID, "NULL tiles/input");
     if (n_tiles > 0xFFFFFFFFull) return fail(MP_ERR_INVALID, "too many tiles");
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     const mp_block* d_tiles = nullptr;
     mp_ctx::TileListRef keep;
     int rc = ctx->device_tiles(tiles, n_tiles, nullptr, keep, &d_tiles, nullptr);  // cached: no per-frame upload
@@ -1350,6 +1396,7 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
         const size_t nt = shard[static_cast<size_t>(r)].size();
         if (nt == 0) continue;
         DeviceGuard g(c->device);
+        LaunchScope record(c);
         std::unique_lock<std::mutex> lk(c->multi_mu, std::defer_lock);
         if (c != c0) lk.lock();
         mp_ctx::MultiBuf& m = c->multi;
@@ -1431,6 +1478,7 @@ int render_multi_impl(mp_ctx* const* ctxs, const mp_scene* const* scenes, int n,
     mp_ctx::TileListRef keep0;
     int rc = c0->device_tiles(order.data(), order.size(), nullptr, keep0, &d_order, nullptr);
     if (rc) return rc;
+    LaunchScope record(c0);
     std::string err;
     // a gather before the last pass shows a preview: the running sums scaled by the samples drawn so far (the shards keep their state)
     const uint32_t mode = (acc && !final_pass) ? ((settings->flags & MP_FLAG_CHUNKED_SUM) ? 2u : 1u) : 0u;
@@ -1471,6 +1519,7 @@ int mp_untile_preview(mp_ctx* ctx, const mp_settings* settings, const mp_block* 
     if (!tiles || !d_tiles_f32) return fail(MP_ERR_INVALID, "NULL tiles/input");
     if (n_tiles > 0xFFFFFFFFull) return fail(MP_ERR_INVALID, "too many tiles");
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     const mp_block* d_tiles = nullptr;
     mp_ctx::TileListRef keep;
     int rc = ctx->device_tiles(tiles, n_tiles, nullptr, keep, &d_tiles, nullptr);
@@ -1495,6 +1544,7 @@ int mp_render_tile(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* 
     const uint32_t ts = settings->tile_size;
     const uint32_t w = tile.max_x - tile.min_x, h = tile.max_y - tile.min_y;
     DeviceGuard g(ctx->device);
+    LaunchScope record(ctx);
     float* d_out = nullptr;
     const size_t bytes = static_cast<size_t>(ts) * ts * 16;
     MP_HIP(hipMalloc(reinterpret_cast<void**>(&d_out), bytes));
@@ -1633,11 +1683,15 @@ void render_worker(mp_render* r, size_t wi) {
             for (size_t i = 0; i < s.n; i++) r->started(r->user, t[i]);  // machinery.rs:75
         e = hipMemcpyAsync(s.d_tiles, t, s.n * sizeof(mp_block), hipMemcpyHostToDevice, s.stream);
         if (e != hipSuccess) { set_error(MP_ERR_HIP, std::string("hipMemcpyAsync(tiles): ") + hipGetErrorString(e)); break; }
-        int rc = render_tiles_device(ctx, scene, r->sampler, st, s.d_tiles, s.n, s.d_f32, s.stream);
-        std::string err;
-        if (!rc) {
-            rc = launch_quantise(s.d_f32, s.d_u8, static_cast<uint64_t>(s.n) * ts * ts, s.stream, err);
-            if (rc) fail(rc, err);
+        int rc;
+        {
+            LaunchScope record(ctx);  // one batch = one record of mp_ctx_last_kernels
+            rc = render_tiles_device(ctx, scene, r->sampler, st, s.d_tiles, s.n, s.d_f32, s.stream);
+            std::string err;
+            if (!rc) {
+                rc = launch_quantise(s.d_f32, s.d_u8, static_cast<uint64_t>(s.n) * ts * ts, s.stream, err);
+                if (rc) fail(rc, err);
+            }
         }
         if (rc) { set_error(rc, mp_last_error()); break; }
         e = r->image_f32 ? hipMemcpyAsync(s.h_f32, s.d_f32, s.n * per_tile * 4, hipMemcpyDeviceToHost, s.stream) : hipSuccess;

@@ -12,6 +12,7 @@
 // the CPU oracle's.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -2821,6 +2822,25 @@ uint64_t mixed_seed(uint64_t seed) {
 
 uint32_t lds_bytes_per_wave(uint32_t stack_cap) { return static_cast<uint32_t>(kQueueFloats * 4 + 8u * stack_cap * 8u); }
 
+// Launch record (diagnostic, mp_ctx_last_kernels): every launch of this file goes through MP_LAUNCH, which notes the kernel's name
+// with its template arguments as written at the site (macro arguments expanded first: MP_LAUNCH_PACKET(16, 7) gives
+// "render_tiles_packet_kernel<16, true, 7>") in the calling thread's list and then launches.  The statement that launches is the
+// statement that records: there is no second selection to keep in step.  Distinct names, in launch order; the usual case is a
+// pointer compare against a handful of literals.
+thread_local std::vector<const char*> t_launched;
+inline void note_launch(const char* name) {
+    for (const char* p : t_launched)
+        if (p == name) return;
+    t_launched.push_back(name);
+}
+#define MP_STR_(x) #x
+#define MP_STR(x) MP_STR_(x)
+#define MP_LAUNCH(kernel, grid, block, lds, stream, ...)                 \
+    do {                                                                 \
+        note_launch(MP_STR(kernel));                                     \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
+    } while (0)
+
 int check(hipError_t e, const char* what, std::string& err) {
     if (e == hipSuccess) return MP_OK;
     err = std::string(what) + ": " + hipGetErrorString(e);
@@ -2828,6 +2848,22 @@ int check(hipError_t e, const char* what, std::string& err) {
 }
 
 }  // namespace
+
+void launch_log_clear() { t_launched.clear(); }
+
+// the names noted since launch_log_clear() on this thread, one per line; a name written in parentheses at its site (a template-id
+// with commas) loses them, and two sites that launch the same instantiation count once
+std::string launch_log_text() {
+    std::vector<std::string> names;
+    for (const char* p : t_launched) {
+        std::string n(p);
+        if (n.size() >= 2 && n.front() == '(' && n.back() == ')') n = n.substr(1, n.size() - 2);
+        if (std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n);
+    }
+    std::string out;
+    for (const std::string& n : names) out += (out.empty() ? "" : "\n") + n;
+    return out;
+}
 
 int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -2872,10 +2908,10 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
 #define MP_LAUNCH_PATHS(SV)                                                                                                  \
     do {                                                                                                                     \
         if (L.scene.inst_count != 0u) {  /* object group: every segment is walked member by member */                        \
-            if (rgb) hipLaunchKernelGGL((render_paths_kernel<SV, true, true>), dim3(grid), dim3(256), lds, st, P);           \
-            else hipLaunchKernelGGL((render_paths_kernel<SV, true, false>), dim3(grid), dim3(256), lds, st, P);              \
-        } else if (rgb) hipLaunchKernelGGL((render_paths_kernel<SV, false, true>), dim3(grid), dim3(256), lds, st, P);       \
-        else hipLaunchKernelGGL((render_paths_kernel<SV, false, false>), dim3(grid), dim3(256), lds, st, P);                 \
+            if (rgb) MP_LAUNCH((render_paths_kernel<SV, true, true>), dim3(grid), dim3(256), lds, st, P);           \
+            else MP_LAUNCH((render_paths_kernel<SV, true, false>), dim3(grid), dim3(256), lds, st, P);              \
+        } else if (rgb) MP_LAUNCH((render_paths_kernel<SV, false, true>), dim3(grid), dim3(256), lds, st, P);       \
+        else MP_LAUNCH((render_paths_kernel<SV, false, false>), dim3(grid), dim3(256), lds, st, P);                 \
     } while (0)
         const bool rgb = L.scene.materials_rgb != 0u;  // a coloured / textured material table: three channels
         if (rgb && L.chunked) { err = "coloured / textured materials are not combined with MP_FLAG_CHUNKED_SUM"; return MP_ERR_UNSUPPORTED; }
@@ -2898,8 +2934,8 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
             const size_t bytes = static_cast<size_t>(pgrid) * 4u * P.pool_stride * sizeof(float);
             rc = check(hipMallocAsync(reinterpret_cast<void**>(&P.pool), bytes, st), "hipMallocAsync(path pool)", err);
             if (rc) return rc;
-            if (nsub == 4) hipLaunchKernelGGL(render_paths_pooled_kernel<4>, dim3(pgrid), dim3(256), plds, st, P);
-            else hipLaunchKernelGGL(render_paths_pooled_kernel<2>, dim3(pgrid), dim3(256), plds, st, P);
+            if (nsub == 4) MP_LAUNCH(render_paths_pooled_kernel<4>, dim3(pgrid), dim3(256), plds, st, P);
+            else MP_LAUNCH(render_paths_pooled_kernel<2>, dim3(pgrid), dim3(256), plds, st, P);
             rc = check(hipGetLastError(), "render_paths_pooled_kernel launch", err);
             (void)hipFreeAsync(P.pool, st);
             return rc;
@@ -2910,8 +2946,8 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
         if (L.mask_cache != 0u && S == 8 && L.scene.inst_count == 0u && L.scene.stack_cap <= L.scene.packet_stack_regs && nspp >= 32u &&
             L.scene.inner_count < (1u << 24) && L.scene.tris_bounded != 0u && L.scene.boxes_ordered != 0u && clds_wave * 4u * MP_PATHS_WPE <= 160u * 1024u) {
             P.lds_per_wave = clds_wave;
-            if (rgb) hipLaunchKernelGGL((render_paths_kernel<8, false, true, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
-            else hipLaunchKernelGGL((render_paths_kernel<8, false, false, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
+            if (rgb) MP_LAUNCH((render_paths_kernel<8, false, true, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
+            else MP_LAUNCH((render_paths_kernel<8, false, false, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
             return check(hipGetLastError(), "render_paths_kernel launch", err);
         }
         if (S == 8) MP_LAUNCH_PATHS(8);
@@ -2923,8 +2959,8 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
     }
     if (L.traversal == 1) {  // MP_FLAG_TRAVERSAL_GROUPS
         const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(L.cu_count) * 8));
-        if (L.scene.inst_count != 0u) hipLaunchKernelGGL((render_tiles_kernel<1, true>), dim3(grid), dim3(256), lds, st, P);
-        else hipLaunchKernelGGL((render_tiles_kernel<1, false>), dim3(grid), dim3(256), lds, st, P);
+        if (L.scene.inst_count != 0u) MP_LAUNCH((render_tiles_kernel<1, true>), dim3(grid), dim3(256), lds, st, P);
+        else MP_LAUNCH((render_tiles_kernel<1, false>), dim3(grid), dim3(256), lds, st, P);
         return check(hipGetLastError(), "render_tiles_kernel launch", err);
     }
     // samples of one pixel in flight per pass: 16 = one DPP row per pixel (ordered sums by row_newbcast), a 2x2 pixel footprint per
@@ -2956,14 +2992,14 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
         // 128-ray walks: two rays per lane (8-pixel units)
         const uint64_t units2 = static_cast<uint64_t>(L.n_tiles) * ((L.tile_size + 3) / 4) * ((L.tile_size + 1) / 2);
         const uint32_t grid2 = static_cast<uint32_t>(std::min<uint64_t>((units2 + 3) / 4, static_cast<uint64_t>(L.cu_count) * 8));
-        hipLaunchKernelGGL((render_tiles_packet2_kernel<6>), dim3(grid2), dim3(256), 0, st, P);
+        MP_LAUNCH((render_tiles_packet2_kernel<6>), dim3(grid2), dim3(256), 0, st, P);
         return check(hipGetLastError(), "render_tiles_packet2_kernel launch", err);
     }
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
 #define MP_LAUNCH_PACKET(SV, W)                                                                                         \
     do {                                                                                                                \
-        if (lds_stack) hipLaunchKernelGGL((render_tiles_packet_kernel<SV, true, W>), dim3(grid), dim3(256), plds, st, P); \
-        else hipLaunchKernelGGL((render_tiles_packet_kernel<SV, false, W>), dim3(grid), dim3(256), 0, st, P);           \
+        if (lds_stack) MP_LAUNCH((render_tiles_packet_kernel<SV, true, W>), dim3(grid), dim3(256), plds, st, P); \
+        else MP_LAUNCH((render_tiles_packet_kernel<SV, false, W>), dim3(grid), dim3(256), 0, st, P);           \
     } while (0)
     // per-unit mask cache of the packet-level child rejection: units of at least four passes, stack in registers, node indices
     // that fit the cache tag, triangle coordinates within the bound of the triangle masks; 3 712 bytes of LDS per wave
@@ -2974,17 +3010,17 @@ int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
     const bool mcache = cache_ok && (S == 4 || S == 8 || S == 16 || S == 32) && nspp >= 4u * static_cast<uint32_t>(S);
     if (mcache) {
         const uint32_t clds = 4u * kMaskCacheDwords * 4u;
-        if (S == 32) hipLaunchKernelGGL((render_tiles_packet_kernel<32, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else if (S == 8) hipLaunchKernelGGL((render_tiles_packet_kernel<8, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else if (S == 4) hipLaunchKernelGGL((render_tiles_packet_kernel<4, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else hipLaunchKernelGGL((render_tiles_packet_kernel<16, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
+        if (S == 32) MP_LAUNCH((render_tiles_packet_kernel<32, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
+        else if (S == 8) MP_LAUNCH((render_tiles_packet_kernel<8, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
+        else if (S == 4) MP_LAUNCH((render_tiles_packet_kernel<4, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
+        else MP_LAUNCH((render_tiles_packet_kernel<16, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
         return check(hipGetLastError(), "render_tiles_packet_kernel launch", err);
     }
     if (obj) {
-        if (S == 16 && lds_stack) hipLaunchKernelGGL((render_tiles_packet_kernel<16, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
-        else if (S == 16) hipLaunchKernelGGL((render_tiles_packet_kernel<16, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
-        else if (lds_stack) hipLaunchKernelGGL((render_tiles_packet_kernel<1, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
-        else hipLaunchKernelGGL((render_tiles_packet_kernel<1, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
+        if (S == 16 && lds_stack) MP_LAUNCH((render_tiles_packet_kernel<16, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
+        else if (S == 16) MP_LAUNCH((render_tiles_packet_kernel<16, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
+        else if (lds_stack) MP_LAUNCH((render_tiles_packet_kernel<1, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
+        else MP_LAUNCH((render_tiles_packet_kernel<1, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
     } else if (S == 64) MP_LAUNCH_PACKET(64, 7);
     else if (S == 32 && big) MP_LAUNCH_PACKET(32, 8);
     else if (S == 32) MP_LAUNCH_PACKET(32, 7);
@@ -3053,7 +3089,7 @@ int launch_render_aov(const RenderLaunch& L, const mp_aov_planes& planes, void* 
     if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stack"; return MP_ERR_UNSUPPORTED; }
     const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / lds));
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
-#define MP_LAUNCH_AOV(...) hipLaunchKernelGGL((render_aov_packet_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds, st, A)
+#define MP_LAUNCH_AOV(...) MP_LAUNCH((render_aov_packet_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds, st, A)
     if (mcache) {
         if (S == 16) MP_LAUNCH_AOV(16, false, 8, false, true);
         else MP_LAUNCH_AOV(4, false, 8, false, true);
@@ -3150,10 +3186,10 @@ int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::stri
             if (rc) break;
             const uint32_t units = ntb * ((ts + 1) / 2) * ((ts + 1) / 2);
             const uint32_t cam_grid = std::min<uint32_t>((units + 3) / 4, cus * per_cu);
-            if (obj && lds_stack) hipLaunchKernelGGL((wf_camera_kernel<true, true>), dim3(cam_grid), dim3(256), plds, st, P);
-            else if (obj) hipLaunchKernelGGL((wf_camera_kernel<false, true>), dim3(cam_grid), dim3(256), 0, st, P);
-            else if (lds_stack) hipLaunchKernelGGL((wf_camera_kernel<true, false>), dim3(cam_grid), dim3(256), plds, st, P);
-            else hipLaunchKernelGGL((wf_camera_kernel<false, false>), dim3(cam_grid), dim3(256), 0, st, P);
+            if (obj && lds_stack) MP_LAUNCH((wf_camera_kernel<true, true>), dim3(cam_grid), dim3(256), plds, st, P);
+            else if (obj) MP_LAUNCH((wf_camera_kernel<false, true>), dim3(cam_grid), dim3(256), 0, st, P);
+            else if (lds_stack) MP_LAUNCH((wf_camera_kernel<true, false>), dim3(cam_grid), dim3(256), plds, st, P);
+            else MP_LAUNCH((wf_camera_kernel<false, false>), dim3(cam_grid), dim3(256), 0, st, P);
             const uint32_t flat_grid = std::min<uint32_t>((P.st.n + 255u) / 256u, cus * 16u);
             WfParams G = P;  // bounce stage: LDS ray queue + eight traversal stacks per wave
             G.lds_per_wave = lds_bytes_per_wave(L.scene.stack_cap);
@@ -3162,18 +3198,18 @@ int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::stri
             const uint32_t gper = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / glds));
             for (uint32_t depth = 1; depth <= L.max_depth; depth++) {
                 P.depth = depth;
-                if (nchan == 3u && obj) hipLaunchKernelGGL((wf_vertex_kernel<3, true>), dim3(flat_grid), dim3(256), 0, st, P);
-                else if (nchan == 3u) hipLaunchKernelGGL((wf_vertex_kernel<3, false>), dim3(flat_grid), dim3(256), 0, st, P);
-                else if (obj) hipLaunchKernelGGL((wf_vertex_kernel<1, true>), dim3(flat_grid), dim3(256), 0, st, P);
-                else hipLaunchKernelGGL((wf_vertex_kernel<1, false>), dim3(flat_grid), dim3(256), 0, st, P);
+                if (nchan == 3u && obj) MP_LAUNCH((wf_vertex_kernel<3, true>), dim3(flat_grid), dim3(256), 0, st, P);
+                else if (nchan == 3u) MP_LAUNCH((wf_vertex_kernel<3, false>), dim3(flat_grid), dim3(256), 0, st, P);
+                else if (obj) MP_LAUNCH((wf_vertex_kernel<1, true>), dim3(flat_grid), dim3(256), 0, st, P);
+                else MP_LAUNCH((wf_vertex_kernel<1, false>), dim3(flat_grid), dim3(256), 0, st, P);
                 if (depth == L.max_depth) break;
-                hipLaunchKernelGGL(wf_scan_kernel, dim3(1), dim3(1024), 0, st, P);
-                hipLaunchKernelGGL(wf_scatter_kernel, dim3(flat_grid), dim3(256), 0, st, P);
-                if (obj) hipLaunchKernelGGL(wf_trace_groups_kernel<true>, dim3(cus * gper), dim3(256), glds, st, G);
-                else hipLaunchKernelGGL(wf_trace_groups_kernel<false>, dim3(cus * gper), dim3(256), glds, st, G);
+                MP_LAUNCH(wf_scan_kernel, dim3(1), dim3(1024), 0, st, P);
+                MP_LAUNCH(wf_scatter_kernel, dim3(flat_grid), dim3(256), 0, st, P);
+                if (obj) MP_LAUNCH(wf_trace_groups_kernel<true>, dim3(cus * gper), dim3(256), glds, st, G);
+                else MP_LAUNCH(wf_trace_groups_kernel<false>, dim3(cus * gper), dim3(256), glds, st, G);
             }
             const uint32_t px_grid = std::min<uint32_t>((ntb * ts * ts + 255u) / 256u, cus * 16u);
-            hipLaunchKernelGGL(wf_accumulate_kernel, dim3(px_grid), dim3(256), 0, st, P);
+            MP_LAUNCH(wf_accumulate_kernel, dim3(px_grid), dim3(256), 0, st, P);
             rc = check(hipGetLastError(), "staged path kernels launch", err);
         }
     }
@@ -3195,8 +3231,8 @@ int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, cons
     if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
     const uint64_t chunks = (n + 63) / 64, want = (chunks + 3) / 4;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(cu_count) * 8));
-    if (sc.inst_count != 0u) hipLaunchKernelGGL(trace_rays_kernel<true>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
-    else hipLaunchKernelGGL(trace_rays_kernel<false>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
+    if (sc.inst_count != 0u) MP_LAUNCH(trace_rays_kernel<true>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
+    else MP_LAUNCH(trace_rays_kernel<false>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
     return check(hipGetLastError(), "trace_rays_kernel launch", err);
 }
 
@@ -3219,15 +3255,15 @@ int launch_query_rays(const DevScene& sc, const float* ox, const float* oy, cons
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(cu_count) * 8));
     const hipStream_t st = static_cast<hipStream_t>(stream);
     const bool obj = sc.inst_count != 0u;
-    if (occluded && obj) hipLaunchKernelGGL((query_rays_kernel<true, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
-    else if (occluded) hipLaunchKernelGGL((query_rays_kernel<false, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
-    else if (obj) hipLaunchKernelGGL((query_rays_kernel<true, kBounded>), dim3(grid), dim3(256), lds, st, P);
-    else hipLaunchKernelGGL((query_rays_kernel<false, kBounded>), dim3(grid), dim3(256), lds, st, P);
+    if (occluded && obj) MP_LAUNCH((query_rays_kernel<true, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
+    else if (occluded) MP_LAUNCH((query_rays_kernel<false, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
+    else if (obj) MP_LAUNCH((query_rays_kernel<true, kBounded>), dim3(grid), dim3(256), lds, st, P);
+    else MP_LAUNCH((query_rays_kernel<false, kBounded>), dim3(grid), dim3(256), lds, st, P);
     return check(hipGetLastError(), "query_rays_kernel launch", err);
 }
 
 int launch_set_u64(unsigned long long* d_ptr, unsigned long long value, void* stream, std::string& err) {
-    hipLaunchKernelGGL(set_u64_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), d_ptr, value);
+    MP_LAUNCH(set_u64_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), d_ptr, value);
     return check(hipGetLastError(), "set_u64_kernel launch", err);
 }
 
@@ -3243,7 +3279,7 @@ int launch_generate_rays(const mp_camera_sampler& s, uint32_t width, uint32_t sp
     G.spp = spp;
     G.seed = mixed_seed(seed);
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + 255) / 256, 8192));
-    hipLaunchKernelGGL(generate_rays_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), G, block, sample, ox,
+    MP_LAUNCH(generate_rays_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), G, block, sample, ox,
                        oy, oz, dx, dy, dz);
     return check(hipGetLastError(), "generate_rays_kernel launch", err);
 }
@@ -3255,7 +3291,7 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
     if (n == 0) return MP_OK;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + 255) / 256, 8192));
     const uint32_t k = std::max<uint32_t>(preview_samples, 1u);
-    hipLaunchKernelGGL(untile_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), width, height, tile_size,
+    MP_LAUNCH(untile_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), width, height, tile_size,
                        d_tiles, n_tiles, d_tiles_f32, d_image_f32, d_image_u8, preview_mode, 1.0f / static_cast<float>(k),
                        1.0 / static_cast<double>(k));
     return check(hipGetLastError(), "untile_kernel launch", err);
@@ -3264,7 +3300,7 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
 int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixels, void* stream, std::string& err) {
     if (n_pixels == 0) return MP_OK;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n_pixels + 255) / 256, 8192));
-    hipLaunchKernelGGL(quantise_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_rgba_f32, d_rgba_u8, n_pixels);
+    MP_LAUNCH(quantise_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_rgba_f32, d_rgba_u8, n_pixels);
     return check(hipGetLastError(), "quantise_kernel launch", err);
 }
 

@@ -202,6 +202,11 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
 
 int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixels, void* stream, std::string& err);
 
+// Launch record (mp_ctx_last_kernels): the launchers above note every kernel they launch, by name, in a list of the calling thread.
+// launch_log_clear() empties it; launch_log_text() gives the distinct names since then, in launch order, one per line.
+void launch_log_clear();
+std::string launch_log_text();
+
 // camera / tiles (host_camera.cpp)
 void camera_default(mp_camera& c);
 void camera_look_at(mp_camera& c, const float eye[3], const float at[3], const float up[3]);

@@ -34,6 +34,17 @@ class Context:
         _lib.check(_lib.lib().mp_ctx_query(self.handle, key.encode(), C.byref(v)))
         return v.value
 
+    def last_kernels(self) -> list:
+        """mp_ctx_last_kernels: the kernels the last launching call on this context launched, by name with their template
+        arguments ("render_tiles_packet_kernel<16, false, 8, false, true>"), distinct names in launch order."""
+        need, cap = C.c_size_t(), 256
+        while True:  # a render worker may file a longer record between two calls: go on until the whole text fits
+            buf = C.create_string_buffer(cap)
+            _lib.check(_lib.lib().mp_ctx_last_kernels(self.handle, buf, cap, C.byref(need)))
+            if need.value < cap:
+                return [n for n in buf.value.decode().split("\n") if n]
+            cap = need.value + 1
+
     def close(self):
         if getattr(self, "handle", None):
             _lib.lib().mp_ctx_destroy(self.handle)

@@ -1,0 +1,155 @@
+"""The dispatch census: one parity case per kernel instantiation that minipath_amd/csrc/kernels.hip can launch, keyed by the name
+mp_ctx_last_kernels reports (the kernel with its template arguments as the launch site writes them).  Plain data, importable
+without a GPU: tests/test_dispatch_census_cpu.py asserts that the keys are exactly the launch sites of kernels.hip, and
+tests/test_gpu_dispatch_matrix.py runs every row on the GPU against the oracle.
+
+A row: api    "render" (reference semantics), "paths" (MP_FLAG_PATHS), "wf" (+ MP_FLAG_WAVEFRONT), "aov" (feature planes),
+              "trace" / "bounded" / "occluded" (ray queries), "rays" (mp_generate_rays), "untile", "async" (mp.render)
+       scene  "teapot", "atrium" (scenes.atrium(1, 0.08): traversal arrays over 1 MB, stack bound 34), "group" ({teapot, soup,
+              sphere}), "sphere", "atrium*2^27" (the atrium scaled until its coordinates pass the triangle masks' 2^30 bound);
+              "+rgb" = under a coloured / checker material table
+       spp    samples per pixel (= samples of the pass)
+       opts   the five launch options, every one set explicitly by every case (DEFAULTS, then the row's)
+       also   other names the same call must report besides the row's key (the staged pipeline's stages, the async worker's render)
+
+Why each row selects its kernel follows launch_render_tiles / launch_render_aov / launch_render_paths_wavefront as they stand;
+the frames of the matrix (72 x 40 and smaller) are all "small launches" there (units * 16 < CUs * 32 * 24), so 32 or more
+samples select 32 in flight.  So the 32-in-flight forms, <32, *, 8> included, are pinned through that rule; the launcher's other
+two ways to them (`big && nspp >= 128`, and the cached table of a launch that is not small) need frames of 12 288 work units
+or more, whose oracle renders do not fit a test: those two selection rules are not exercised by name."""
+
+DEFAULTS = {"packet_samples_in_flight": 0, "packet_mask_cache": 1, "packet_stack_registers": 64, "packet_rays_per_lane": 1, "paths_pooled": 1}
+LDS_REGS = {"teapot": 3, "group": 3, "atrium": 8}  # packet_stack_registers below the scene's stack bound (22, 22, 34)
+
+# kernels.hip launches these too, but they are utilities, not instantiations of the render / query paths: no row
+EXCLUDED = {
+    "set_u64_kernel": "one-thread store that initialises the ray-segment counter; its value is asserted by every counted case",
+}
+
+
+def launched(ctx):
+    """ctx.last_kernels() without the utilities of EXCLUDED: FrameRenderer always passes a segment counter, so its render calls
+    report set_u64_kernel before the render kernel"""
+    return [k for k in ctx.last_kernels() if k not in EXCLUDED]
+
+
+# launch sites of the test probes, outside kernels.hip and outside the library (libmp_probe.so / libmp_mask_probe.so)
+PROBE_FILES = {
+    "probe.hip": "test probe of ray_math.h (tests/test_ray_math_gpu.py): its kernels are the test, not the product",
+    "mask_probe.hip": "test probe of mask_cache.h (tests/test_mask_cache_gpu.py): its kernels are the test, not the product",
+}
+
+
+def _row(api, scene, spp, also=(), **opts):
+    short = {"samples": "packet_samples_in_flight", "cache": "packet_mask_cache", "regs": "packet_stack_registers",
+             "lanes": "packet_rays_per_lane", "pooled": "paths_pooled", "traversal": "traversal"}
+    o = {short[k]: v for k, v in opts.items()}
+    trav = o.pop("traversal", "packets")
+    return {"api": api, "scene": scene, "spp": spp, "opts": o, "traversal": trav, "also": tuple(also)}
+
+
+CASES = {}
+
+# ---- launch_render_tiles, packets: <S, LDS_STACK, W>; automatic S from the pass's samples, mask cache off ------------------------
+for _s, _spp in ((1, 1), (2, 3), (4, 5), (8, 9), (16, 17), (32, 33)):
+    CASES[f"render_tiles_packet_kernel<{_s}, false, 7>"] = _row("render", "teapot", _spp, cache=0)
+    CASES[f"render_tiles_packet_kernel<{_s}, true, 7>"] = _row("render", "teapot", _spp, cache=0, regs=LDS_REGS["teapot"])
+# 64 in flight only on request
+CASES["render_tiles_packet_kernel<64, false, 7>"] = _row("render", "teapot", 70, cache=0, samples=64)
+CASES["render_tiles_packet_kernel<64, true, 7>"] = _row("render", "teapot", 70, cache=0, samples=64, regs=LDS_REGS["teapot"])
+# big scene: eight waves per SIMD
+CASES["render_tiles_packet_kernel<16, false, 8>"] = _row("render", "atrium", 17, cache=0)
+CASES["render_tiles_packet_kernel<16, true, 8>"] = _row("render", "atrium", 17, cache=0, regs=LDS_REGS["atrium"])
+CASES["render_tiles_packet_kernel<32, false, 8>"] = _row("render", "atrium", 33, cache=0)
+CASES["render_tiles_packet_kernel<32, true, 8>"] = _row("render", "atrium", 33, cache=0, regs=LDS_REGS["atrium"])
+# mask cache (default on): S follows the sample count, units of at least four passes
+CASES["render_tiles_packet_kernel<4, false, 8, false, true>"] = _row("render", "teapot", 16)
+CASES["render_tiles_packet_kernel<8, false, 8, false, true>"] = _row("render", "teapot", 33)
+CASES["render_tiles_packet_kernel<16, false, 8, false, true>"] = _row("render", "teapot", 64)
+CASES["render_tiles_packet_kernel<32, false, 8, false, true>"] = _row("render", "teapot", 128)
+# object group: 16 in flight from 16 samples on, else one
+CASES["render_tiles_packet_kernel<16, false, 6, true>"] = _row("render", "group", 17)
+CASES["render_tiles_packet_kernel<16, true, 6, true>"] = _row("render", "group", 17, regs=LDS_REGS["group"])
+CASES["render_tiles_packet_kernel<1, false, 6, true>"] = _row("render", "group", 3)
+CASES["render_tiles_packet_kernel<1, true, 6, true>"] = _row("render", "group", 3, regs=LDS_REGS["group"])
+# two rays per lane: 16 in flight, stack in registers
+CASES["render_tiles_packet2_kernel<6>"] = _row("render", "teapot", 17, cache=0, lanes=2)
+# ---- launch_render_tiles, 8-lane groups ------------------------------------------------------------------------------------------
+CASES["render_tiles_kernel<1, false>"] = _row("render", "teapot", 5, traversal="groups")
+CASES["render_tiles_kernel<1, true>"] = _row("render", "group", 5, traversal="groups")
+# ---- launch_render_tiles, paths: <S, OBJ, RGB>, S from the pass's samples: 1, 2-3, 4-7, >= 8 ------------------------------------
+for _s, _spp in ((1, 1), (2, 3), (4, 6), (8, 9)):
+    for _obj in (False, True):
+        for _rgb in (False, True):
+            _scene = ("group" if _obj else "teapot") + ("+rgb" if _rgb else "")
+            CASES[f"render_paths_kernel<{_s}, {str(_obj).lower()}, {str(_rgb).lower()}>"] = _row("paths", _scene, _spp)
+# camera pass on the cached packet walk: 32 samples or more, plain scene, stack in registers
+CASES["render_paths_kernel<8, false, false, true>"] = _row("paths", "teapot", 32)
+CASES["render_paths_kernel<8, false, true, true>"] = _row("paths", "teapot+rgb", 32)
+CASES["render_paths_pooled_kernel<2>"] = _row("paths", "teapot", 16, pooled=2)
+CASES["render_paths_pooled_kernel<4>"] = _row("paths", "teapot", 32, pooled=3)
+# ---- launch_render_aov: <S, LDS_STACK, W[, OBJ[, MCACHE]]> -----------------------------------------------------------------------
+CASES["render_aov_packet_kernel<16, false, 8, false, true>"] = _row("aov", "teapot", 64)
+CASES["render_aov_packet_kernel<4, false, 8, false, true>"] = _row("aov", "teapot", 16)
+CASES["render_aov_packet_kernel<16, true, 6, true>"] = _row("aov", "group+rgb", 16, regs=LDS_REGS["group"])
+CASES["render_aov_packet_kernel<16, false, 6, true>"] = _row("aov", "group+rgb", 16)
+CASES["render_aov_packet_kernel<1, true, 6, true>"] = _row("aov", "group+rgb", 3, regs=LDS_REGS["group"])
+CASES["render_aov_packet_kernel<1, false, 6, true>"] = _row("aov", "group+rgb", 3)
+CASES["render_aov_packet_kernel<16, true, 8>"] = _row("aov", "teapot", 16, regs=LDS_REGS["teapot"])
+CASES["render_aov_packet_kernel<1, true, 8>"] = _row("aov", "teapot", 3, regs=LDS_REGS["teapot"])
+CASES["render_aov_packet_kernel<16, false, 8>"] = _row("aov", "teapot", 16, cache=0)
+CASES["render_aov_packet_kernel<4, false, 8>"] = _row("aov", "teapot", 5)
+CASES["render_aov_packet_kernel<1, false, 8>"] = _row("aov", "teapot", 3)
+# ---- launch_render_paths_wavefront: camera <LDS_STACK, OBJ>, vertex <NCHAN, OBJ>, trace <OBJ>, scan / scatter / accumulate -------
+
+
+def _wf(obj, lds, rgb):
+    """(scene, options, every kernel the staged pipeline launches for it)"""
+    b = lambda x: str(bool(x)).lower()  # noqa: E731
+    scene = ("group" if obj else "teapot") + ("+rgb" if rgb else "")
+    names = [f"wf_camera_kernel<{b(lds)}, {b(obj)}>", f"wf_vertex_kernel<{3 if rgb else 1}, {b(obj)}>", "wf_scan_kernel", "wf_scatter_kernel",
+             f"wf_trace_groups_kernel<{b(obj)}>", "wf_accumulate_kernel"]
+    return scene, ({"regs": LDS_REGS["group" if obj else "teapot"]} if lds else {}), names
+
+
+for _key, _cfg in (("wf_camera_kernel<false, false>", (0, 0, 0)), ("wf_camera_kernel<true, false>", (0, 1, 0)),
+                   ("wf_camera_kernel<false, true>", (1, 0, 0)), ("wf_camera_kernel<true, true>", (1, 1, 0)),
+                   ("wf_vertex_kernel<1, false>", (0, 1, 0)), ("wf_vertex_kernel<1, true>", (1, 1, 0)),
+                   ("wf_vertex_kernel<3, false>", (0, 0, 1)), ("wf_vertex_kernel<3, true>", (1, 0, 1)),
+                   ("wf_trace_groups_kernel<false>", (0, 0, 0)), ("wf_trace_groups_kernel<true>", (1, 0, 1)),
+                   ("wf_scan_kernel", (0, 1, 1)), ("wf_scatter_kernel", (1, 1, 1)), ("wf_accumulate_kernel", (1, 0, 0))):
+    _scene, _o, _names = _wf(*_cfg)
+    assert _key in _names
+    CASES[_key] = _row("wf", _scene, 5, also=[n for n in _names if n != _key], **_o)
+# ---- ray queries -----------------------------------------------------------------------------------------------------------------
+CASES["trace_rays_kernel<false>"] = _row("trace", "teapot", 0)
+CASES["trace_rays_kernel<true>"] = _row("trace", "group", 0)
+CASES["query_rays_kernel<false, kBounded>"] = _row("bounded", "teapot", 0)
+CASES["query_rays_kernel<true, kBounded>"] = _row("bounded", "group", 0)
+CASES["query_rays_kernel<false, kAnyHit>"] = _row("occluded", "teapot", 0)
+CASES["query_rays_kernel<true, kAnyHit>"] = _row("occluded", "group", 0)
+# ---- the rest of the C ABI's kernels ---------------------------------------------------------------------------------------------
+CASES["generate_rays_kernel"] = _row("rays", "teapot", 16)
+CASES["untile_kernel"] = _row("untile", "teapot", 5)
+CASES["quantise_kernel"] = _row("async", "teapot", 5, also=["render_tiles_packet_kernel<4, false, 7>"])
+
+# ---- gate cases: the mask cache is on and the sample count asks for it, one guard refuses: the UNCACHED name must be reported -----
+GATES = {
+    "triangle coordinates beyond 2^30 (tris_bounded)": ("render_tiles_packet_kernel<32, false, 8>", _row("render", "atrium*2^27", 64)),
+    "a sphere (kind != 0)": ("render_tiles_packet_kernel<32, false, 7>", _row("render", "sphere", 64)),
+    "an object group": ("render_tiles_packet_kernel<16, false, 6, true>", _row("render", "group", 64)),
+    "the stack beyond the registers": ("render_tiles_packet_kernel<32, true, 7>", _row("render", "teapot", 64, regs=LDS_REGS["teapot"])),
+    "15 samples against 16": ("render_tiles_packet_kernel<8, false, 7>", _row("render", "teapot", 15)),
+    "a pass of 4 S - 1 samples": ("render_tiles_packet_kernel<16, false, 7>", _row("render", "teapot", 63, samples=16)),
+    "the option off": ("render_tiles_packet_kernel<32, false, 7>", _row("render", "teapot", 64, cache=0)),
+}
+
+# ---- ragged MP_FLAG_ACCUMULATE passes: selection follows the samples of the PASS; 70 samples per pixel in all --------------------
+RAGGED = {
+    "packets": (_row("render", "teapot", 70), [
+        (40, "render_tiles_packet_kernel<8, false, 8, false, true>"), (17, "render_tiles_packet_kernel<4, false, 8, false, true>"),
+        (8, "render_tiles_packet_kernel<8, false, 7>"), (4, "render_tiles_packet_kernel<4, false, 7>"), (1, "render_tiles_packet_kernel<1, false, 7>")]),
+    "paths": (_row("paths", "teapot", 70), [
+        (40, "render_paths_kernel<8, false, false, true>"), (17, "render_paths_kernel<8, false, false>"), (6, "render_paths_kernel<4, false, false>"),
+        (4, "render_paths_kernel<4, false, false>"), (2, "render_paths_kernel<2, false, false>"), (1, "render_paths_kernel<1, false, false>")]),
+}

@@ -10,6 +10,7 @@ import pytest
 import minipath_amd as mp
 from minipath_amd import _lib, scenes
 from tests import aov_model, meshes
+from tests import dispatch_cases as dc
 from tests.aov_model import bits
 from tests.conftest import TEAPOT
 
@@ -37,12 +38,15 @@ def _options(ctx, samples=0, cache=1, regs=64):
     ctx.set_option("packet_stack_registers", regs)
 
 
-def _images(obj, cam, st, tiles=None, **which):
-    """render_aov + untile_plane of every plane asked for: {name: [h, w, 4] numpy}; ids as uint32"""
+def _images(obj, cam, st, tiles=None, names=None, **which):
+    """render_aov + untile_plane of every plane asked for: {name: [h, w, 4] numpy}; ids as uint32.  names: a list that receives the
+    kernels the feature-plane launch reported"""
     import torch
 
     fr = mp.FrameRenderer(mp.Scene(obj), cam, st, tiles=tiles)
     out = fr.render_aov(**which)
+    if names is not None:
+        names += dc.launched(obj.ctx)
     img = {k: fr.untile_plane(v) for k, v in out.items()}
     torch.cuda.synchronize()
     return {k: (v.cpu().numpy().view(np.uint32) if k == "ids" else v.cpu().numpy()) for k, v in img.items()}
@@ -136,18 +140,30 @@ def test_planes_equal_the_model(ctx, oracle, name):
             _same(_images(gpu, cam, mp.RenderSettings(17, spp2, r2, seed=seed)), w2, (name, spp2))
 
 
-# 6. sample counts that reach every S the launcher selects, with and without the mask cache
+# 6. sample counts that reach every S the launcher selects, with and without the mask cache: the template arguments of
+# render_aov_packet_kernel each count must report (mask cache on, off, stack in LDS), and together they are every form of the
+# kernel that a scene without members can select
+AOV_FORMS = {1: ("1, false, 8", "1, false, 8", "1, true, 8"), 2: ("1, false, 8", "1, false, 8", "1, true, 8"),
+             3: ("1, false, 8", "1, false, 8", "1, true, 8"), 10: ("4, false, 8", "4, false, 8", "1, true, 8"),
+             16: ("4, false, 8, false, true", "16, false, 8", "16, true, 8"), 33: ("4, false, 8, false, true", "16, false, 8", "16, true, 8"),
+             64: ("16, false, 8, false, true", "16, false, 8", "16, true, 8"), 100: ("16, false, 8, false, true", "16, false, 8", "16, true, 8")}
+assert {f"render_aov_packet_kernel<{f}>" for forms in AOV_FORMS.values() for f in forms} == \
+    {k for k, row in dc.CASES.items() if row["api"] == "aov" and not row["scene"].startswith("group")}
+
+
 @pytest.mark.parametrize("spp", [1, 2, 3, 10, 16, 33, 64, 100])
 def test_sample_counts_equal_the_model(ctx, oracle, spp):
     gpu, cam, isect, table = _scene("checker" if spp in (3, 33) else "teapot", ctx, oracle)
     res = (16, 12)
     want = _model(oracle, cam, isect, res, spp, 4, table)
+    names = []
     for cache in (1, 0):
         _options(ctx, cache=cache)
-        _same(_images(gpu, cam, mp.RenderSettings(16, spp, res, seed=4)), want, (spp, cache))
+        _same(_images(gpu, cam, mp.RenderSettings(16, spp, res, seed=4), names=names), want, (spp, cache))
     _options(ctx, regs=4)
-    _same(_images(gpu, cam, mp.RenderSettings(16, spp, res, seed=4)), want, (spp, "lds stack"))
+    _same(_images(gpu, cam, mp.RenderSettings(16, spp, res, seed=4), names=names), want, (spp, "lds stack"))
     _options(ctx)
+    assert names == [f"render_aov_packet_kernel<{f}>" for f in AOV_FORMS[spp]], names
 
 
 def test_planes_do_not_depend_on_launch_options(ctx):

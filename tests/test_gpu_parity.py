@@ -10,6 +10,7 @@ import pytest
 
 import minipath_amd as mp
 from tests import meshes
+from tests.dispatch_cases import launched
 from tests.conftest import TEAPOT
 
 pytestmark = pytest.mark.gpu
@@ -457,6 +458,9 @@ def test_packet_stack_in_lds(oracle, teapot_oracle_bvh, regs):
         st = mp.RenderSettings(64, 8, (256, 256), seed=SEED, max_depth=max_depth)
         fr = mp.FrameRenderer(scene, mp.Camera.teapot_view(), st, tiles=[mp.ScreenBlock(64, 96, 128, 160)])
         got = fr.render()[0].cpu().numpy()
+        lds = "true" if regs == 3 else "false"  # 8 samples: 8 in flight, too few passes for the mask cache
+        want = "render_paths_kernel<8, false, false>" if max_depth else f"render_tiles_packet_kernel<8, {lds}, 7>"
+        assert launched(c) == [want]
         s = oracle.build_sampler(oracle.teapot_camera(), 256, 256)
         if max_depth:
             of, _, _ = teapot_oracle_bvh.render_tile_paths(s, 256, 256, 8, SEED, max_depth, 64, 96, 128, 160)
@@ -697,7 +701,9 @@ def test_progressive_passes_equal_single_launch(teapot, tmp_path, max_depth, tra
 
 def test_two_rays_per_lane_walk_is_bit_identical(teapot, oracle, teapot_oracle_bvh):
     """mp_ctx_set_option("packet_rays_per_lane", 2): 128-ray walks (two rays per lane, 4x2-pixel units) must give the frame of the
-    64-ray walk and of the oracle bit for bit, incl. clipped tiles, ragged progressive passes and the chunked accumulation rule."""
+    64-ray walk and of the oracle bit for bit, incl. clipped tiles, ragged progressive passes and the chunked accumulation rule.
+    The option takes effect only where the launcher has 16 samples in flight (a plain scene, stack in registers); at other
+    counts it is ignored and the 64-ray kernels run, so the test asks for 16 and checks the name of every launch."""
     import torch
 
     ctx = teapot.object.ctx
@@ -706,9 +712,13 @@ def test_two_rays_per_lane_walk_is_bit_identical(teapot, oracle, teapot_oracle_b
     of, ou8, *_ = teapot_oracle_bvh.render_image_mt(oracle.build_sampler(oracle.teapot_camera(), *res), res[0], res[1], spp, SEED, 32, 8)
     try:
         ctx.set_option("packet_rays_per_lane", 2)
+        # the 128-ray walk exists for 16 samples in flight only; left to itself the launcher gives these sample counts 4, 8 or 32
+        # (mask cache, small launch) and the 64-ray kernels -- so 16 are asked for, and the name of what ran is checked
+        ctx.set_option("packet_samples_in_flight", 16)
         st = mp.RenderSettings(32, spp, res, seed=SEED)
         fr = mp.FrameRenderer(teapot, cam, st)
         fr.render()
+        assert launched(ctx) == ["render_tiles_packet2_kernel<6>"]
         img, img8 = fr.untile()
         torch.cuda.synchronize()
         assert np.array_equal(bits(img.cpu().numpy()), bits(of)) and np.array_equal(img8.cpu().numpy(), ou8)
@@ -716,17 +726,23 @@ def test_two_rays_per_lane_walk_is_bit_identical(teapot, oracle, teapot_oracle_b
         nxt = 0
         for count in (16, 5, 0):
             nxt = pr.render_pass(nxt, count)
+            assert launched(ctx) == ["render_tiles_packet2_kernel<6>"]
         img2, _ = pr.untile()
         torch.cuda.synchronize()
         assert torch.equal(img2.view(torch.int32), img.view(torch.int32))
         stc = mp.RenderSettings(32, 300, (64, 40), seed=SEED, chunked_sum=True)
-        two = mp.FrameRenderer(teapot, cam, stc); two.render(); a, _ = two.untile()
+        two = mp.FrameRenderer(teapot, cam, stc); two.render()
+        assert launched(ctx) == ["render_tiles_packet2_kernel<6>"]
+        a, _ = two.untile()
         ctx.set_option("packet_rays_per_lane", 1)
-        one = mp.FrameRenderer(teapot, cam, stc); one.render(); b, _ = one.untile()
+        one = mp.FrameRenderer(teapot, cam, stc); one.render()
+        assert launched(ctx) == ["render_tiles_packet_kernel<16, false, 8, false, true>"]
+        b, _ = one.untile()
         torch.cuda.synchronize()
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     finally:
         ctx.set_option("packet_rays_per_lane", 1)
+        ctx.set_option("packet_samples_in_flight", 0)
 
 
 def test_samples_in_flight_do_not_change_the_frame(teapot, oracle, teapot_oracle_bvh):
@@ -744,6 +760,10 @@ def test_samples_in_flight_do_not_change_the_frame(teapot, oracle, teapot_oracle
             ctx.set_option("packet_samples_in_flight", s_in_flight)
             fr = mp.FrameRenderer(teapot, cam, st)
             fr.render()
+            # S in the kernel's name is the S asked for, every time; 37 samples are four passes or more of 4 and of 8: those two run
+            # on the mask cache's form
+            form = "8, false, true" if s_in_flight in (4, 8) else "7"
+            assert launched(ctx) == [f"render_tiles_packet_kernel<{s_in_flight}, false, {form}>"]
             img, _ = fr.untile()
             torch.cuda.synchronize()
             assert np.array_equal(bits(img.cpu().numpy()), bits(want)), s_in_flight

@@ -7,6 +7,7 @@ import pytest
 
 import minipath_amd as mp
 from tests import meshes
+from tests.dispatch_cases import launched
 from tests.conftest import TEAPOT
 
 pytestmark = pytest.mark.gpu
@@ -231,6 +232,11 @@ def test_pooled_path_kernel_modes(oracle, teapot_oracle_bvh, mode):
         st = mp.RenderSettings(64, spp, res, seed=SEED, max_depth=depth)
         fr = mp.FrameRenderer(teapot, cam, st, tiles=[mp.ScreenBlock(*tile)])
         buf = fr.render()
+        # the kernel the mode selects: pooled with two passes (mode 2) or four from 32 samples on (mode 3); mode 0 the one-pass kernel,
+        # its camera pass on the cached packet walk from 32 samples on
+        want = {0: "render_paths_kernel<8, false, false, true>" if spp >= 32 else "render_paths_kernel<8, false, false>",
+                2: "render_paths_pooled_kernel<2>", 3: "render_paths_pooled_kernel<4>" if spp >= 32 else "render_paths_pooled_kernel<2>"}[mode]
+        assert launched(c) == [want]
         torch.cuda.synchronize()
         tw, th = tile[2] - tile[0], tile[3] - tile[1]
         of, _, seg = teapot_oracle_bvh.render_tile_paths(oracle.build_sampler(oracle.teapot_camera(), *res), res[0], res[1], spp, SEED, depth, *tile)
@@ -298,6 +304,8 @@ def test_packet_mask_cache(oracle, teapot_oracle_bvh, mode):
         of, ou8, _, seg, _ = teapot_oracle_bvh.render_image_mt(oracle.build_sampler(oc, *res), res[0], res[1], spp, SEED, 32, 8)
         fr = mp.FrameRenderer(teapot, cam, mp.RenderSettings(32, spp, res, seed=SEED))
         fr.render()
+        # every one of these frames has units of four passes or more: the cached form with the cache on, the plain one with it off
+        assert launched(c) == [f"render_tiles_packet_kernel<{sflight}, false, " + ("8, false, true>" if mode else "7>")]
         img, u8 = fr.untile()
         torch.cuda.synchronize()
         assert np.array_equal(bits(img.cpu().numpy()), bits(of)), (mode, fnum, spp)
@@ -316,7 +324,12 @@ def test_packet_mask_cache(oracle, teapot_oracle_bvh, mode):
         spp = 96
         of, _, _, _, _ = orc.render_image_mt(oracle.build_sampler(oc, *res), res[0], res[1], spp, 3, 32, 8)
         fr = mp.FrameRenderer(scene, cam, mp.RenderSettings(32, spp, res, seed=3))
-        nxt = fr.render_pass(0, 70); fr.render_pass(nxt)
+        # automatic samples in flight: the cache's table gives the pass of 70 samples 16 and the one of 26 four; without the cache
+        # these small launches get 32 from 32 samples on, else 16
+        nxt = fr.render_pass(0, 70)
+        assert launched(c) == ["render_tiles_packet_kernel<16, false, 8, false, true>" if mode else "render_tiles_packet_kernel<32, false, 7>"]
+        fr.render_pass(nxt)
+        assert launched(c) == ["render_tiles_packet_kernel<4, false, 8, false, true>" if mode else "render_tiles_packet_kernel<16, false, 7>"]
         img, _ = fr.untile()
         torch.cuda.synchronize()
         assert np.array_equal(bits(img.cpu().numpy()), bits(of)), (mode, eye)
