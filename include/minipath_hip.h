@@ -228,7 +228,7 @@ int mp_ctx_query(mp_ctx *ctx, const char *key, uint64_t *value);
 /* Diagnostics.  The kernels launched by the last call on ctx that launched any (mp_render_tile, mp_render_tiles_device*,
  * mp_render_aov_device, mp_untile*, mp_trace_rays*, mp_occluded_rays, mp_generate_rays; one call = one record, so mp_render_tile
  * reports its render kernel only, and mp_render_tiles_device_ex with d_ray_segments the counter's set_u64_kernel before the render
- * kernel): the kernels' names with their template arguments as the launcher writes them, e.g.
+ * kernel): the kernels' names with their template arguments as the library's kernel table writes them, e.g.
  * "render_tiles_packet_kernel<16, false, 8, false, true>", distinct names in launch order, separated by '\n' (the staged path
  * evaluation launches several kernels per bounce: each name once).  The record is made by the statement that launches, so a
  * test can pin which instantiation an input selects; it is made before the launch, so a launch that the runtime refuses (the

@@ -16,7 +16,9 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
+#include <type_traits>
 
+#include "launch_plan.h"
 #include "mp_internal.h"
 #include "ray_math.h"
 
@@ -2820,340 +2822,176 @@ uint64_t mixed_seed(uint64_t seed) {
     return z ^ (z >> 31);
 }
 
-uint32_t lds_bytes_per_wave(uint32_t stack_cap) { return static_cast<uint32_t>(kQueueFloats * 4 + 8u * stack_cap * 8u); }
-
-// Launch record (diagnostic, mp_ctx_last_kernels): every launch of this file goes through MP_LAUNCH, which notes the kernel's name
-// with its template arguments as written at the site (macro arguments expanded first: MP_LAUNCH_PACKET(16, 7) gives
-// "render_tiles_packet_kernel<16, true, 7>") in the calling thread's list and then launches.  The statement that launches is the
-// statement that records: there is no second selection to keep in step.  Distinct names, in launch order; the usual case is a
-// pointer compare against a handful of literals.
-thread_local std::vector<const char*> t_launched;
-inline void note_launch(const char* name) {
-    for (const char* p : t_launched)
-        if (p == name) return;
-    t_launched.push_back(name);
-}
-#define MP_STR_(x) #x
-#define MP_STR(x) MP_STR_(x)
-#define MP_LAUNCH(kernel, grid, block, lds, stream, ...)                 \
-    do {                                                                 \
-        note_launch(MP_STR(kernel));                                     \
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
-    } while (0)
-
 int check(hipError_t e, const char* what, std::string& err) {
     if (e == hipSuccess) return MP_OK;
     err = std::string(what) + ": " + hipGetErrorString(e);
     return MP_ERR_HIP;
 }
 
+static_assert(kPlanQueueFloats == kQueueFloats && kPlanMaskCacheDwords == kMaskCacheDwords && kPlanDirBins == kDirBins &&
+                  kPlanPoolFloatsPerSub == pool_floats_per_wave(1),
+              "launch_plan.h sizes the launches with the device code's constants");
+
+// Launch record (diagnostic, mp_ctx_last_kernels) and the one place that launches: launch() notes the row's name -- the kernel with
+// its template arguments as kernel_table.h writes them -- in the calling thread's list and then launches that row's kernel.  The
+// statement that launches is the statement that records: there is no second selection to keep in step.  Distinct names, in launch
+// order; the usual case is a compare against a handful of ids.
+thread_local std::vector<KernelId> t_launched;
+inline void note_launch(KernelId id) {
+    if (std::find(t_launched.begin(), t_launched.end(), id) == t_launched.end()) t_launched.push_back(id);
+}
+#define MP_LAUNCH(id, kernel, grid, block, lds, stream, ...)               \
+    do {                                                                   \
+        note_launch(id);                                                   \
+        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
+    } while (0)
+
+int launched(KernelId id, std::string& err) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MP_OK : check(e, (std::string(kKernelNames[id]) + " launch").c_str(), err);
+}
+
+// Launches row `id` of the table with these arguments.  A row whose kernel does not take them is not instantiated for them; an id
+// of such a row is a programming error (MP_ERR_INVALID).
+template <class... Args>
+int launch(KernelId id, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t st, std::string& err, const Args&... args) {
+    switch (id) {
+#define MP_X(row, ...)                                                                   \
+    case row:                                                                            \
+        if constexpr (std::is_invocable_v<decltype(&__VA_ARGS__), Args...>) {            \
+            MP_LAUNCH(row, (__VA_ARGS__), dim3(grid), dim3(block), lds, st, args...);    \
+            return launched(row, err);                                                   \
+        }                                                                                \
+        break;
+        MP_KERNEL_TABLE(MP_X)
+#undef MP_X
+        default: break;
+    }
+    err = "kernel table: no such kernel for these arguments";
+    return MP_ERR_INVALID;
+}
+
+void fill_raygen(RayGen& G, const mp_camera_sampler& s, uint32_t width, uint32_t spp, uint64_t seed) {
+    G.s = s;
+    G.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
+    G.width = width;
+    G.spp = spp;
+    G.seed = mixed_seed(seed);
+}
+
+// the fields RenderParams and WfParams share
+template <class Params>
+void fill_common(Params& P, const RenderLaunch& L) {
+    P.scene = L.scene;
+    fill_raygen(P.gen, L.sampler, L.width, L.spp, L.seed);
+    P.tile_size = L.tile_size;
+    P.out = L.d_out;
+    P.inv_spp = 1.0f / static_cast<float>(L.spp);
+    P.chunked = L.chunked ? 1u : 0u;
+    P.max_depth = L.max_depth;
+    P.segments = L.d_segments;
+}
+
+void fill_render(RenderParams& P, const RenderLaunch& L, const LaunchPlan& plan) {
+    fill_common(P, L);
+    P.tiles = L.d_tiles;
+    P.n_tiles = L.n_tiles;
+    P.counter = L.d_counter;
+    P.s_begin = L.pass_begin;
+    P.s_end = L.pass_end;
+    P.carry_in = L.carry_in ? 1u : 0u;
+    P.finalize = L.finalize ? 1u : 0u;
+    P.tile_order = L.d_tile_order;
+    P.tile_cost = L.d_tile_cost;
+    P.pool = nullptr;
+    P.pool_stride = plan.pool_stride;
+    P.lds_per_wave = plan.lds_per_wave;
+}
+
+template <class Plan>
+int refused(const Plan& plan, std::string& err) {
+    err = plan.error;
+    return plan.rc;
+}
+
+int zero_work_queues(const RenderLaunch& L, hipStream_t st, std::string& err) {
+    return check(hipMemsetAsync(L.d_counter, 0, kWorkQueues * kWorkQueueStride * sizeof(uint32_t), st), "hipMemsetAsync(counter)", err);
+}
+
 }  // namespace
 
 void launch_log_clear() { t_launched.clear(); }
 
-// the names noted since launch_log_clear() on this thread, one per line; a name written in parentheses at its site (a template-id
-// with commas) loses them, and two sites that launch the same instantiation count once
+// the names noted since launch_log_clear() on this thread, one per line
 std::string launch_log_text() {
-    std::vector<std::string> names;
-    for (const char* p : t_launched) {
-        std::string n(p);
-        if (n.size() >= 2 && n.front() == '(' && n.back() == ')') n = n.substr(1, n.size() - 2);
-        if (std::find(names.begin(), names.end(), n) == names.end()) names.push_back(n);
-    }
     std::string out;
-    for (const std::string& n : names) out += (out.empty() ? "" : "\n") + n;
+    for (KernelId id : t_launched) out += (out.empty() ? "" : "\n") + std::string(kKernelNames[id]);
     return out;
 }
 
 int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (L.n_tiles == 0) return MP_OK;
+    const LaunchPlan plan = plan_render_tiles(L);
+    if (plan.rc) return refused(plan, err);
     RenderParams P;
-    P.scene = L.scene;
-    P.gen.s = L.sampler;
-    P.gen.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
-    P.gen.width = L.width;
-    P.gen.spp = L.spp;
-    P.gen.seed = mixed_seed(L.seed);
-    P.tiles = L.d_tiles;
-    P.n_tiles = L.n_tiles;
-    P.tile_size = L.tile_size;
-    P.out = L.d_out;
-    P.counter = L.d_counter;
-    P.inv_spp = 1.0f / static_cast<float>(L.spp);
-    P.s_begin = L.pass_begin;
-    P.s_end = L.pass_end;
-    P.carry_in = L.carry_in ? 1u : 0u;
-    P.finalize = L.finalize ? 1u : 0u;
-    P.chunked = L.chunked ? 1u : 0u;
-    P.tile_order = L.d_tile_order;
-    P.tile_cost = L.d_tile_cost;
-    P.max_depth = L.max_depth;
-    P.segments = L.d_segments;
-    P.pool = nullptr;
-    P.pool_stride = 0;
-    P.lds_per_wave = lds_bytes_per_wave(L.scene.stack_cap);
-    const uint32_t lds = P.lds_per_wave * 4;
-    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
-    int rc = check(hipMemsetAsync(L.d_counter, 0, kWorkQueues * kWorkQueueStride * sizeof(uint32_t), st), "hipMemsetAsync(counter)", err);
+    fill_render(P, L, plan);
+    int rc = zero_work_queues(L, st, err);
     if (rc) return rc;
-    const uint64_t units = static_cast<uint64_t>(L.n_tiles) * ((L.tile_size + 7) / 8) * ((L.tile_size + 7) / 8);
-    const uint64_t want = (units + 3) / 4;
-    if (L.max_depth > 0 && L.scene.kind != 0u) { err = "the path extension is defined for TriangleBvh scenes only"; return MP_ERR_UNSUPPORTED; }
-    if (L.max_depth > 0) {  // build-defined path extension
-        const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / lds));
-        const uint32_t nspp = L.pass_end - L.pass_begin;  // samples per pixel in this launch
-        const int S = nspp >= 8 ? 8 : nspp >= 4 ? 4 : nspp >= 2 ? 2 : 1;  // 16 in flight measured slower here (teapot depth 8: 17.1 vs 15.7 ms)
-        const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
-#define MP_LAUNCH_PATHS(SV)                                                                                                  \
-    do {                                                                                                                     \
-        if (L.scene.inst_count != 0u) {  /* object group: every segment is walked member by member */                        \
-            if (rgb) MP_LAUNCH((render_paths_kernel<SV, true, true>), dim3(grid), dim3(256), lds, st, P);           \
-            else MP_LAUNCH((render_paths_kernel<SV, true, false>), dim3(grid), dim3(256), lds, st, P);              \
-        } else if (rgb) MP_LAUNCH((render_paths_kernel<SV, false, true>), dim3(grid), dim3(256), lds, st, P);       \
-        else MP_LAUNCH((render_paths_kernel<SV, false, false>), dim3(grid), dim3(256), lds, st, P);                 \
-    } while (0)
-        const bool rgb = L.scene.materials_rgb != 0u;  // a coloured / textured material table: three channels
-        if (rgb && L.chunked) { err = "coloured / textured materials are not combined with MP_FLAG_CHUNKED_SUM"; return MP_ERR_UNSUPPORTED; }
-        // pooled form (render_paths_pooled_kernel): plain TriangleBvh scenes with a grey table, at least two passes of 8 samples.
-        // By default for scenes whose traversal arrays exceed 1 MB -- there the 8-lane-group walk dominates and the longer queue
-        // pays (stand-in depth 8: 564 against 628 ms); on the teapot, where most paths end after one or two segments and ray
-        // generation and shading dominate, the one-pass kernel is faster (50.2 against 54.3 ms).  paths_pooled: 0 never, 1 auto,
-        // 2 always with two passes, 3 always with up to four.
-        const bool big_scene = (static_cast<uint64_t>(L.scene.inner_count) * 256u + static_cast<uint64_t>(L.scene.packet_count) * 384u) > (1u << 20);
-        const bool pooled = L.paths_pooled >= 2u || (L.paths_pooled == 1u && big_scene);
-        if (pooled && !rgb && L.scene.inst_count == 0u && L.max_depth >= 2 && nspp >= 16) {
-            const int nsub = (nspp >= 32 && L.paths_pooled != 2u) ? 4 : 2;
-            const uint32_t plds_wave = 8u * L.scene.stack_cap * 8u;  // the eight traversal stacks; the ray queue lives in the pool
-            P.lds_per_wave = plds_wave;
-            const uint32_t plds = plds_wave * 4u;
-            if (plds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
-            const uint32_t pper_cu = plds ? std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / plds)) : 8u;
-            const uint32_t pgrid = static_cast<uint32_t>(std::min<uint64_t>(want * 8, static_cast<uint64_t>(L.cu_count) * pper_cu));
-            P.pool_stride = pool_floats_per_wave(nsub);
-            const size_t bytes = static_cast<size_t>(pgrid) * 4u * P.pool_stride * sizeof(float);
-            rc = check(hipMallocAsync(reinterpret_cast<void**>(&P.pool), bytes, st), "hipMallocAsync(path pool)", err);
-            if (rc) return rc;
-            if (nsub == 4) MP_LAUNCH(render_paths_pooled_kernel<4>, dim3(pgrid), dim3(256), plds, st, P);
-            else MP_LAUNCH(render_paths_pooled_kernel<2>, dim3(pgrid), dim3(256), plds, st, P);
-            rc = check(hipGetLastError(), "render_paths_pooled_kernel launch", err);
-            (void)hipFreeAsync(P.pool, st);
-            return rc;
-        }
-        // camera pass on the cached packet walk (MaskCache): plain scenes whose stack fits the registers, units of at least four
-        // passes, and only while the cache's 3 712 bytes per wave leave the six resident waves per SIMD their LDS
-        const uint32_t clds_wave = P.lds_per_wave + static_cast<uint32_t>(kMaskCacheDwords) * 4u;
-        if (L.mask_cache != 0u && S == 8 && L.scene.inst_count == 0u && L.scene.stack_cap <= L.scene.packet_stack_regs && nspp >= 32u &&
-            L.scene.inner_count < (1u << 24) && L.scene.tris_bounded != 0u && L.scene.boxes_ordered != 0u && clds_wave * 4u * MP_PATHS_WPE <= 160u * 1024u) {
-            P.lds_per_wave = clds_wave;
-            if (rgb) MP_LAUNCH((render_paths_kernel<8, false, true, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
-            else MP_LAUNCH((render_paths_kernel<8, false, false, true>), dim3(grid), dim3(256), clds_wave * 4u, st, P);
-            return check(hipGetLastError(), "render_paths_kernel launch", err);
-        }
-        if (S == 8) MP_LAUNCH_PATHS(8);
-        else if (S == 4) MP_LAUNCH_PATHS(4);
-        else if (S == 2) MP_LAUNCH_PATHS(2);
-        else MP_LAUNCH_PATHS(1);
-#undef MP_LAUNCH_PATHS
-        return check(hipGetLastError(), "render_paths_kernel launch", err);
+    if (plan.pool_bytes) {
+        rc = check(hipMallocAsync(reinterpret_cast<void**>(&P.pool), plan.pool_bytes, st), "hipMallocAsync(path pool)", err);
+        if (rc) return rc;
     }
-    if (L.traversal == 1) {  // MP_FLAG_TRAVERSAL_GROUPS
-        const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(L.cu_count) * 8));
-        if (L.scene.inst_count != 0u) MP_LAUNCH((render_tiles_kernel<1, true>), dim3(grid), dim3(256), lds, st, P);
-        else MP_LAUNCH((render_tiles_kernel<1, false>), dim3(grid), dim3(256), lds, st, P);
-        return check(hipGetLastError(), "render_tiles_kernel launch", err);
-    }
-    // samples of one pixel in flight per pass: 16 = one DPP row per pixel (ordered sums by row_newbcast), a 2x2 pixel footprint per
-    // wave and 4-pixel work units (measured best on MI355X for full frames: profiles/r01_notes.md)
-    const uint32_t nspp = L.pass_end - L.pass_begin;  // samples per pixel in this launch
-    int S = nspp >= 16 ? 16 : nspp >= 8 ? 8 : nspp >= 4 ? 4 : nspp >= 2 ? 2 : 1;
-    // small launches (a rank's shard of a multi-GPU frame): 2-pixel units, so that the tail of the launch is half as long
-    const bool small_launch = units * 16u < static_cast<uint64_t>(L.cu_count) * 32u * 24u;
-    if (nspp >= 32 && small_launch) S = 32;
-    // scenes whose traversal arrays exceed the 16 KB scalar data cache by far run 8 waves per SIMD, and at many samples per pixel
-    // 32 samples of a pixel in flight (a 1x2 pixel footprint: measured 42.1 against 42.6 ms on the metric's frame, tools/s_sweep.py)
-    const bool big = (static_cast<uint64_t>(L.scene.inner_count) * 256u + static_cast<uint64_t>(L.scene.packet_count) * 384u) > (1u << 20);
-    if (big && nspp >= 128) S = 32;
-    const bool obj = L.scene.inst_count != 0u;  // object group: one packet walk per member (instantiated for 16 and 1 samples in flight)
-    const bool lds_stack = L.scene.stack_cap > L.scene.packet_stack_regs;
-    // The per-unit mask cache (MaskCache) wants units of at least four passes: with it, the samples in flight follow the sample
-    // count -- 16 from 64 spp on (metric's frame, 256 spp: 21.7 ms against 22.1 with 32; 64 spp: 6.3 against 6.4 with 8), 8 for
-    // 32-63 spp (3.5 against 5.5 ms uncached at 32 spp), 4 for 16-31 (2.2 against 2.9 ms at 16 spp) -- and small launches keep
-    // their 2-pixel units where those still have four passes
-    const bool cache_ok = L.mask_cache != 0u && !lds_stack && !obj && L.scene.kind == 0u && L.scene.inner_count < (1u << 24) && L.scene.tris_bounded != 0u;
-    if (cache_ok && nspp >= 16) S = (small_launch && nspp >= 128) ? 32 : nspp >= 64 ? 16 : nspp >= 32 ? 8 : 4;
-    if (L.packet_samples) S = static_cast<int>(std::min<uint32_t>(L.packet_samples, 64u));
-    if (obj) S = (S >= 16 && nspp >= 16) ? 16 : 1;
-    P.lds_per_wave = lds_stack ? (L.scene.stack_cap - L.scene.packet_stack_regs) * 16u : 0u;  // one uint4 per entry beyond the register stack
-    const uint32_t plds = P.lds_per_wave * 4;
-    if (plds > 160 * 1024) { err = "scene too deep for the LDS traversal stack"; return MP_ERR_UNSUPPORTED; }
-    const uint32_t per_cu = plds ? std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / plds)) : 8u;
-    if (S == 16 && L.rays_per_lane == 2 && !lds_stack && !obj && L.scene.kind == 0u && L.scene.stack_cap <= 64u) {
-        // 128-ray walks: two rays per lane (8-pixel units)
-        const uint64_t units2 = static_cast<uint64_t>(L.n_tiles) * ((L.tile_size + 3) / 4) * ((L.tile_size + 1) / 2);
-        const uint32_t grid2 = static_cast<uint32_t>(std::min<uint64_t>((units2 + 3) / 4, static_cast<uint64_t>(L.cu_count) * 8));
-        MP_LAUNCH((render_tiles_packet2_kernel<6>), dim3(grid2), dim3(256), 0, st, P);
-        return check(hipGetLastError(), "render_tiles_packet2_kernel launch", err);
-    }
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
-#define MP_LAUNCH_PACKET(SV, W)                                                                                         \
-    do {                                                                                                                \
-        if (lds_stack) MP_LAUNCH((render_tiles_packet_kernel<SV, true, W>), dim3(grid), dim3(256), plds, st, P); \
-        else MP_LAUNCH((render_tiles_packet_kernel<SV, false, W>), dim3(grid), dim3(256), 0, st, P);           \
-    } while (0)
-    // per-unit mask cache of the packet-level child rejection: units of at least four passes, stack in registers, node indices
-    // that fit the cache tag, triangle coordinates within the bound of the triangle masks; 3 712 bytes of LDS per wave
-#ifndef MP_MCACHE_WPE
-#define MP_MCACHE_WPE 8
-#endif
-    // (every scene: with the triangle masks the teapot's frame gains too -- 9.9 against 11.8 ms)
-    const bool mcache = cache_ok && (S == 4 || S == 8 || S == 16 || S == 32) && nspp >= 4u * static_cast<uint32_t>(S);
-    if (mcache) {
-        const uint32_t clds = 4u * kMaskCacheDwords * 4u;
-        if (S == 32) MP_LAUNCH((render_tiles_packet_kernel<32, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else if (S == 8) MP_LAUNCH((render_tiles_packet_kernel<8, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else if (S == 4) MP_LAUNCH((render_tiles_packet_kernel<4, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        else MP_LAUNCH((render_tiles_packet_kernel<16, false, MP_MCACHE_WPE, false, true>), dim3(grid), dim3(256), clds, st, P);
-        return check(hipGetLastError(), "render_tiles_packet_kernel launch", err);
-    }
-    if (obj) {
-        if (S == 16 && lds_stack) MP_LAUNCH((render_tiles_packet_kernel<16, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
-        else if (S == 16) MP_LAUNCH((render_tiles_packet_kernel<16, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
-        else if (lds_stack) MP_LAUNCH((render_tiles_packet_kernel<1, true, 6, true>), dim3(grid), dim3(256), plds, st, P);
-        else MP_LAUNCH((render_tiles_packet_kernel<1, false, 6, true>), dim3(grid), dim3(256), 0, st, P);
-    } else if (S == 64) MP_LAUNCH_PACKET(64, 7);
-    else if (S == 32 && big) MP_LAUNCH_PACKET(32, 8);
-    else if (S == 32) MP_LAUNCH_PACKET(32, 7);
-    else if (S == 16 && big) MP_LAUNCH_PACKET(16, 8);
-    else if (S == 16) MP_LAUNCH_PACKET(16, 7);
-    else if (S == 8) MP_LAUNCH_PACKET(8, 7);
-    else if (S == 4) MP_LAUNCH_PACKET(4, 7);
-    else if (S == 2) MP_LAUNCH_PACKET(2, 7);
-    else MP_LAUNCH_PACKET(1, 7);
-#undef MP_LAUNCH_PACKET
-    return check(hipGetLastError(), "render_tiles_packet_kernel launch", err);
+    rc = launch(plan.kernel, plan.grid, 256, plan.lds, st, err, P);
+    if (P.pool) (void)hipFreeAsync(P.pool, st);
+    return rc;
 }
 
-// mp_render_aov_device: the packet kernel with feature planes (render_aov_packet_kernel).  Samples in flight and mask cache follow
-// launch_render_tiles' rules on a shorter list of instantiations: S = 16 from 16 samples per pixel on, 4 from 4 on, else 1;
-// with the mask cache (same conditions: stack in registers, no object group, units of at least four passes) 16 from 64 samples on
-// and 4 for 16-63; object groups and LDS-stack scenes 16 or 1.  A packet_samples_in_flight request is rounded down to these.
+// mp_render_aov_device: the whole frame's samples in one launch, means written, no path extension
 int launch_render_aov(const RenderLaunch& L, const mp_aov_planes& planes, void* stream, std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (L.n_tiles == 0) return MP_OK;
+    const LaunchPlan plan = plan_render_aov(L);
+    if (plan.rc) return refused(plan, err);
     AovParams A;
     RenderParams& P = A.r;
-    P.scene = L.scene;
-    P.gen.s = L.sampler;
-    P.gen.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
-    P.gen.width = L.width;
-    P.gen.spp = L.spp;
-    P.gen.seed = mixed_seed(L.seed);
-    P.tiles = L.d_tiles;
-    P.n_tiles = L.n_tiles;
-    P.tile_size = L.tile_size;
+    fill_render(P, L, plan);
     P.out = nullptr;
-    P.counter = L.d_counter;
-    P.inv_spp = 1.0f / static_cast<float>(L.spp);
     P.s_begin = 0;
     P.s_end = L.spp;
     P.carry_in = 0u;
     P.finalize = 1u;
     P.chunked = 0u;
-    P.tile_order = L.d_tile_order;
-    P.tile_cost = L.d_tile_cost;
     P.max_depth = 0;
     P.segments = nullptr;
-    P.pool = nullptr;
-    P.pool_stride = 0;
     A.shade = planes.d_shade;
     A.normal = planes.d_normal;
     A.albedo = planes.d_albedo;
     A.ids = planes.d_ids;
-    int rc = check(hipMemsetAsync(L.d_counter, 0, kWorkQueues * kWorkQueueStride * sizeof(uint32_t), st), "hipMemsetAsync(counter)", err);
+    const int rc = zero_work_queues(L, st, err);
     if (rc) return rc;
-    const uint64_t units = static_cast<uint64_t>(L.n_tiles) * ((L.tile_size + 7) / 8) * ((L.tile_size + 7) / 8);
-    const uint64_t want = (units + 3) / 4;
-    const uint32_t nspp = L.spp;
-    const bool obj = L.scene.inst_count != 0u;
-    const bool lds_stack = L.scene.stack_cap > L.scene.packet_stack_regs;
-    int S = nspp >= 16 ? 16 : nspp >= 4 ? 4 : 1;
-    const bool cache_ok = L.mask_cache != 0u && !lds_stack && !obj && L.scene.kind == 0u && L.scene.inner_count < (1u << 24) && L.scene.tris_bounded != 0u;
-    if (cache_ok && nspp >= 16) S = nspp >= 64 ? 16 : 4;
-    if (L.packet_samples) S = L.packet_samples >= 16u ? 16 : L.packet_samples >= 4u ? 4 : 1;
-    if ((obj || lds_stack) && S == 4) S = 1;
-    const bool mcache = cache_ok && S >= 4 && nspp >= 4u * static_cast<uint32_t>(S);
-    P.lds_per_wave = lds_stack ? (L.scene.stack_cap - L.scene.packet_stack_regs) * 16u : 0u;
-    const uint32_t park = 4u * (64u / static_cast<uint32_t>(S)) * 32u;  // the parked sums of the block's four waves
-    const uint32_t lds = park + (mcache ? 4u * kMaskCacheDwords * 4u : P.lds_per_wave * 4u);
-    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stack"; return MP_ERR_UNSUPPORTED; }
-    const uint32_t per_cu = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / lds));
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want * S, static_cast<uint64_t>(L.cu_count) * per_cu));
-#define MP_LAUNCH_AOV(...) MP_LAUNCH((render_aov_packet_kernel<__VA_ARGS__>), dim3(grid), dim3(256), lds, st, A)
-    if (mcache) {
-        if (S == 16) MP_LAUNCH_AOV(16, false, 8, false, true);
-        else MP_LAUNCH_AOV(4, false, 8, false, true);
-    } else if (obj) {
-        if (S == 16 && lds_stack) MP_LAUNCH_AOV(16, true, 6, true);
-        else if (S == 16) MP_LAUNCH_AOV(16, false, 6, true);
-        else if (lds_stack) MP_LAUNCH_AOV(1, true, 6, true);
-        else MP_LAUNCH_AOV(1, false, 6, true);
-    } else if (lds_stack) {
-        if (S == 16) MP_LAUNCH_AOV(16, true, 8);
-        else MP_LAUNCH_AOV(1, true, 8);
-    } else if (S == 16) MP_LAUNCH_AOV(16, false, 8);
-    else if (S == 4) MP_LAUNCH_AOV(4, false, 8);
-    else MP_LAUNCH_AOV(1, false, 8);
-#undef MP_LAUNCH_AOV
-    return check(hipGetLastError(), "render_aov_packet_kernel launch", err);
+    return launch(plan.kernel, plan.grid, 256, plan.lds, st, err, A);
 }
 
 int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::string& err) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (L.n_tiles == 0) return MP_OK;
-    if (L.scene.kind != 0u || L.max_depth == 0) { err = "the staged path evaluation needs MP_FLAG_PATHS and a TriangleBvh scene or an object group"; return MP_ERR_UNSUPPORTED; }
-    const bool obj = L.scene.inst_count != 0u;
+    const WavefrontPlan plan = plan_render_paths_wavefront(L);
+    if (plan.rc) return refused(plan, err);
     WfParams P;
-    P.scene = L.scene;
-    P.gen.s = L.sampler;
-    P.gen.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
-    P.gen.width = L.width;
-    P.gen.spp = L.spp;
-    P.gen.seed = mixed_seed(L.seed);
-    P.tile_size = L.tile_size;
-    P.max_depth = L.max_depth;
-    P.out = L.d_out;
-    P.inv_spp = 1.0f / static_cast<float>(L.spp);
-    P.segments = L.d_segments;
-    P.chunked = L.chunked ? 1u : 0u;
-    const bool lds_stack = L.scene.stack_cap > L.scene.packet_stack_regs;
-    P.lds_per_wave = lds_stack ? (L.scene.stack_cap - L.scene.packet_stack_regs) * 16u : 0u;  // one uint4 per entry beyond the register stack
-    const uint32_t plds = P.lds_per_wave * 4;
-    if (plds > 160 * 1024) { err = "scene too deep for the LDS traversal stack"; return MP_ERR_UNSUPPORTED; }
-    const uint32_t per_cu = plds ? std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / plds)) : 8u;
-    // a batch = tb tiles x sc samples, about two million paths: enough rays per (tile, direction bin) to fill packets
-    const uint32_t ts = L.tile_size, nspp = L.pass_end - L.pass_begin;
-    const uint32_t sc = std::min<uint32_t>(nspp, 64u);
-    const uint64_t per_tile = static_cast<uint64_t>(ts) * ts * sc;
-    if (per_tile > (1ull << 28)) { err = "tile_size too large for the staged path evaluation"; return MP_ERR_UNSUPPORTED; }
-    const uint32_t tb = static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(L.n_tiles, (1ull << 21) / per_tile)));
-    const uint32_t n_max = static_cast<uint32_t>(per_tile * tb), nbins = tb * kDirBins;
-    // workspace: rng 32 + ray 24 + thr, L 8 (24 for three channels) + hit 16 + flags, key, idx 12 = 92 (108) bytes per path,
-    // stream-ordered allocation
-    const uint32_t nchan = L.scene.materials_rgb ? 3u : 1u;
-    if (nchan == 3u && L.chunked) { err = "coloured / textured materials are not combined with MP_FLAG_CHUNKED_SUM"; return MP_ERR_UNSUPPORTED; }
-    P.st.nchan = nchan;
-    const size_t n64 = (static_cast<size_t>(n_max) + 63) & ~static_cast<size_t>(63);
-    const size_t bytes = n64 * (88 + 8 * nchan) + (static_cast<size_t>(nbins) + 64) * 4 * 3;
+    fill_common(P, L);
+    P.lds_per_wave = plan.cam_lds_per_wave;
+    P.st.nchan = plan.nchan;
+    const size_t n64 = plan.n64, bin_bytes = (static_cast<size_t>(plan.nbins) + 64) * 4;
     unsigned char* ws = nullptr;
-    int rc = check(hipMallocAsync(reinterpret_cast<void**>(&ws), bytes, st), "hipMallocAsync(path state)", err);
+    int rc = check(hipMallocAsync(reinterpret_cast<void**>(&ws), plan.ws_bytes, st), "hipMallocAsync(path state)", err);
     if (rc) return rc;
     unsigned char* w = ws;
     auto take = [&](size_t b) { unsigned char* r = w; w += b; return r; };
     P.st.rng = reinterpret_cast<uint64_t*>(take(n64 * 32));
     P.st.ray = reinterpret_cast<float*>(take(n64 * 24));
-    P.st.thr = reinterpret_cast<float*>(take(n64 * 4 * nchan));
-    P.st.L = reinterpret_cast<float*>(take(n64 * 4 * nchan));
+    P.st.thr = reinterpret_cast<float*>(take(n64 * 4 * plan.nchan));
+    P.st.L = reinterpret_cast<float*>(take(n64 * 4 * plan.nchan));
     P.st.hit_t = reinterpret_cast<float*>(take(n64 * 4));
     P.st.hit_prim = reinterpret_cast<uint32_t*>(take(n64 * 4));
     P.st.hit_u = reinterpret_cast<float*>(take(n64 * 4));
@@ -3162,109 +3000,83 @@ int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::stri
     P.st.flags = reinterpret_cast<uint32_t*>(take(n64 * 4));
     P.st.key = reinterpret_cast<uint32_t*>(take(n64 * 4));
     P.st.idx = reinterpret_cast<uint32_t*>(take(n64 * 4));
-    P.st.hist = reinterpret_cast<uint32_t*>(take((static_cast<size_t>(nbins) + 64) * 4));
-    P.st.offs = reinterpret_cast<uint32_t*>(take((static_cast<size_t>(nbins) + 64) * 4));
-    P.st.cursor = reinterpret_cast<uint32_t*>(take((static_cast<size_t>(nbins) + 64) * 4));
-    const uint32_t cus = static_cast<uint32_t>(L.cu_count);
-    for (uint32_t tile_base = 0; tile_base < L.n_tiles && !rc; tile_base += tb) {
-        const uint32_t ntb = std::min(tb, L.n_tiles - tile_base);
+    P.st.hist = reinterpret_cast<uint32_t*>(take(bin_bytes));
+    P.st.offs = reinterpret_cast<uint32_t*>(take(bin_bytes));
+    P.st.cursor = reinterpret_cast<uint32_t*>(take(bin_bytes));
+    for (uint32_t tile_base = 0; tile_base < L.n_tiles && !rc; tile_base += plan.tb) {
+        const uint32_t ntb = std::min(plan.tb, L.n_tiles - tile_base);
+        const WavefrontBatch B = plan.batch(ntb);
         P.tiles = L.d_tiles + tile_base;
         P.n_tiles = ntb;
         P.tile_base = tile_base;
-        for (uint32_t s0 = L.pass_begin; s0 < L.pass_end && !rc; s0 += sc) {
+        for (uint32_t s0 = L.pass_begin; s0 < L.pass_end && !rc; s0 += plan.sc) {
             P.s0 = s0;
-            P.sc = sc;
+            P.sc = plan.sc;
             P.s_end = L.pass_end;
-            P.st.n = static_cast<uint32_t>(per_tile * ntb);
-            P.st.nbins = ntb * kDirBins;
+            P.st.n = B.n;
+            P.st.nbins = B.nbins;
             P.carry_in = (L.carry_in || s0 > L.pass_begin) ? 1u : 0u;
-            P.finalize = (L.finalize && s0 + sc >= L.pass_end) ? 1u : 0u;
+            P.finalize = (L.finalize && s0 + plan.sc >= L.pass_end) ? 1u : 0u;
             rc = check(hipMemsetAsync(P.st.hist, 0, (static_cast<size_t>(P.st.nbins) + 1) * 4, st), "hipMemsetAsync(histogram)", err);
             if (rc) break;
             // path slots of pixels outside a clipped tile are never written by the camera stage: they must read as dead
             rc = check(hipMemsetAsync(P.st.flags, 0, static_cast<size_t>(P.st.n) * 4, st), "hipMemsetAsync(path flags)", err);
             if (rc) break;
-            const uint32_t units = ntb * ((ts + 1) / 2) * ((ts + 1) / 2);
-            const uint32_t cam_grid = std::min<uint32_t>((units + 3) / 4, cus * per_cu);
-            if (obj && lds_stack) MP_LAUNCH((wf_camera_kernel<true, true>), dim3(cam_grid), dim3(256), plds, st, P);
-            else if (obj) MP_LAUNCH((wf_camera_kernel<false, true>), dim3(cam_grid), dim3(256), 0, st, P);
-            else if (lds_stack) MP_LAUNCH((wf_camera_kernel<true, false>), dim3(cam_grid), dim3(256), plds, st, P);
-            else MP_LAUNCH((wf_camera_kernel<false, false>), dim3(cam_grid), dim3(256), 0, st, P);
-            const uint32_t flat_grid = std::min<uint32_t>((P.st.n + 255u) / 256u, cus * 16u);
+            rc = launch(plan.camera, B.cam_grid, 256, plan.cam_lds, st, err, P);
             WfParams G = P;  // bounce stage: LDS ray queue + eight traversal stacks per wave
-            G.lds_per_wave = lds_bytes_per_wave(L.scene.stack_cap);
-            const uint32_t glds = G.lds_per_wave * 4;
-            if (glds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; rc = MP_ERR_UNSUPPORTED; break; }
-            const uint32_t gper = std::max<uint32_t>(1, std::min<uint32_t>(8, (160u * 1024u) / glds));
-            for (uint32_t depth = 1; depth <= L.max_depth; depth++) {
+            G.lds_per_wave = plan.trace_lds_per_wave;
+            for (uint32_t depth = 1; depth <= L.max_depth && !rc; depth++) {
                 P.depth = depth;
-                if (nchan == 3u && obj) MP_LAUNCH((wf_vertex_kernel<3, true>), dim3(flat_grid), dim3(256), 0, st, P);
-                else if (nchan == 3u) MP_LAUNCH((wf_vertex_kernel<3, false>), dim3(flat_grid), dim3(256), 0, st, P);
-                else if (obj) MP_LAUNCH((wf_vertex_kernel<1, true>), dim3(flat_grid), dim3(256), 0, st, P);
-                else MP_LAUNCH((wf_vertex_kernel<1, false>), dim3(flat_grid), dim3(256), 0, st, P);
-                if (depth == L.max_depth) break;
-                MP_LAUNCH(wf_scan_kernel, dim3(1), dim3(1024), 0, st, P);
-                MP_LAUNCH(wf_scatter_kernel, dim3(flat_grid), dim3(256), 0, st, P);
-                if (obj) MP_LAUNCH(wf_trace_groups_kernel<true>, dim3(cus * gper), dim3(256), glds, st, G);
-                else MP_LAUNCH(wf_trace_groups_kernel<false>, dim3(cus * gper), dim3(256), glds, st, G);
+                rc = launch(plan.vertex, B.flat_grid, 256, 0, st, err, P);
+                if (rc || depth == L.max_depth) break;
+                rc = launch(K_WF_SCAN, 1, 1024, 0, st, err, P);
+                if (!rc) rc = launch(K_WF_SCATTER, B.flat_grid, 256, 0, st, err, P);
+                if (!rc) rc = launch(plan.trace, plan.trace_grid, 256, plan.trace_lds, st, err, G);
             }
-            const uint32_t px_grid = std::min<uint32_t>((ntb * ts * ts + 255u) / 256u, cus * 16u);
-            MP_LAUNCH(wf_accumulate_kernel, dim3(px_grid), dim3(256), 0, st, P);
-            rc = check(hipGetLastError(), "staged path kernels launch", err);
+            if (!rc) rc = launch(K_WF_ACCUMULATE, B.px_grid, 256, 0, st, err, P);
         }
     }
     (void)hipFreeAsync(ws, st);
     return rc;
 }
 
-int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx,
-                      const float* dy, const float* dz, uint64_t n, const mp_hits_soa& hits, int cu_count, void* stream,
-                      std::string& err) {
+namespace {
+// the three ray queries: one plan, one fill; mp_trace_rays launches on the TraceParams alone
+int launch_rays(QueryKind kind, const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count, void* stream,
+                std::string& err) {
     if (n == 0) return MP_OK;
-    TraceParams P;
-    P.scene = sc;
-    P.ox = ox; P.oy = oy; P.oz = oz; P.dx = dx; P.dy = dy; P.dz = dz;
-    P.n = n;
-    P.hits = hits;
-    P.lds_per_wave = lds_bytes_per_wave(sc.stack_cap);
-    const uint32_t lds = P.lds_per_wave * 4;
-    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
-    const uint64_t chunks = (n + 63) / 64, want = (chunks + 3) / 4;
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(cu_count) * 8));
-    if (sc.inst_count != 0u) MP_LAUNCH(trace_rays_kernel<true>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
-    else MP_LAUNCH(trace_rays_kernel<false>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), P);
-    return check(hipGetLastError(), "trace_rays_kernel launch", err);
-}
-
-// grid and LDS as launch_trace_rays; occluded != NULL: the any-hit kernel (hits unused), otherwise the bounded closest hit
-int launch_query_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
-                      const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count,
-                      void* stream, std::string& err) {
-    if (n == 0) return MP_OK;
+    const LaunchPlan plan = plan_ray_query(sc, n, cu_count, kind);
+    if (plan.rc) return refused(plan, err);
     QueryParams P;
     P.tr.scene = sc;
     P.tr.ox = ox; P.tr.oy = oy; P.tr.oz = oz; P.tr.dx = dx; P.tr.dy = dy; P.tr.dz = dz;
     P.tr.n = n;
     P.tr.hits = hits ? *hits : mp_hits_soa{};
-    P.tr.lds_per_wave = lds_bytes_per_wave(sc.stack_cap);
+    P.tr.lds_per_wave = plan.lds_per_wave;
     P.tmax = tmax;
     P.occluded = occluded;
-    const uint32_t lds = P.tr.lds_per_wave * 4;
-    if (lds > 160 * 1024) { err = "scene too deep for the LDS traversal stacks"; return MP_ERR_UNSUPPORTED; }
-    const uint64_t chunks = (n + 63) / 64, want = (chunks + 3) / 4;
-    const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>(want, static_cast<uint64_t>(cu_count) * 8));
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool obj = sc.inst_count != 0u;
-    if (occluded && obj) MP_LAUNCH((query_rays_kernel<true, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
-    else if (occluded) MP_LAUNCH((query_rays_kernel<false, kAnyHit>), dim3(grid), dim3(256), lds, st, P);
-    else if (obj) MP_LAUNCH((query_rays_kernel<true, kBounded>), dim3(grid), dim3(256), lds, st, P);
-    else MP_LAUNCH((query_rays_kernel<false, kBounded>), dim3(grid), dim3(256), lds, st, P);
-    return check(hipGetLastError(), "query_rays_kernel launch", err);
+    if (kind == kQueryClosest) return launch(plan.kernel, plan.grid, 256, plan.lds, st, err, P.tr);
+    return launch(plan.kernel, plan.grid, 256, plan.lds, st, err, P);
+}
+}  // namespace
+
+int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx,
+                      const float* dy, const float* dz, uint64_t n, const mp_hits_soa& hits, int cu_count, void* stream,
+                      std::string& err) {
+    return launch_rays(kQueryClosest, sc, ox, oy, oz, dx, dy, dz, nullptr, n, &hits, nullptr, cu_count, stream, err);
+}
+
+// occluded != NULL: the any-hit kernel (hits unused), otherwise the bounded closest hit
+int launch_query_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
+                      const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count,
+                      void* stream, std::string& err) {
+    return launch_rays(occluded ? kQueryAnyHit : kQueryBounded, sc, ox, oy, oz, dx, dy, dz, tmax, n, hits, occluded, cu_count, stream, err);
 }
 
 int launch_set_u64(unsigned long long* d_ptr, unsigned long long value, void* stream, std::string& err) {
-    MP_LAUNCH(set_u64_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), d_ptr, value);
-    return check(hipGetLastError(), "set_u64_kernel launch", err);
+    return launch(K_SET_U64, 1, 1, 0, static_cast<hipStream_t>(stream), err, d_ptr, value);
 }
 
 int launch_generate_rays(const mp_camera_sampler& s, uint32_t width, uint32_t spp, uint64_t seed, mp_block block,
@@ -3273,15 +3085,9 @@ int launch_generate_rays(const mp_camera_sampler& s, uint32_t width, uint32_t sp
     const uint64_t n = static_cast<uint64_t>(block.max_x - block.min_x) * (block.max_y - block.min_y);
     if (n == 0) return MP_OK;
     RayGen G;
-    G.s = s;
-    G.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
-    G.width = width;
-    G.spp = spp;
-    G.seed = mixed_seed(seed);
+    fill_raygen(G, s, width, spp, seed);
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + 255) / 256, 8192));
-    MP_LAUNCH(generate_rays_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), G, block, sample, ox,
-                       oy, oz, dx, dy, dz);
-    return check(hipGetLastError(), "generate_rays_kernel launch", err);
+    return launch(K_GENERATE_RAYS, grid, 256, 0, static_cast<hipStream_t>(stream), err, G, block, sample, ox, oy, oz, dx, dy, dz);
 }
 
 int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_block* d_tiles, uint32_t n_tiles,
@@ -3291,17 +3097,14 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
     if (n == 0) return MP_OK;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n + 255) / 256, 8192));
     const uint32_t k = std::max<uint32_t>(preview_samples, 1u);
-    MP_LAUNCH(untile_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), width, height, tile_size,
-                       d_tiles, n_tiles, d_tiles_f32, d_image_f32, d_image_u8, preview_mode, 1.0f / static_cast<float>(k),
-                       1.0 / static_cast<double>(k));
-    return check(hipGetLastError(), "untile_kernel launch", err);
+    return launch(K_UNTILE, grid, 256, 0, static_cast<hipStream_t>(stream), err, width, height, tile_size, d_tiles, n_tiles, d_tiles_f32,
+                  d_image_f32, d_image_u8, preview_mode, 1.0f / static_cast<float>(k), 1.0 / static_cast<double>(k));
 }
 
 int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixels, void* stream, std::string& err) {
     if (n_pixels == 0) return MP_OK;
     const uint32_t grid = static_cast<uint32_t>(std::min<uint64_t>((n_pixels + 255) / 256, 8192));
-    MP_LAUNCH(quantise_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), d_rgba_f32, d_rgba_u8, n_pixels);
-    return check(hipGetLastError(), "quantise_kernel launch", err);
+    return launch(K_QUANTISE, grid, 256, 0, static_cast<hipStream_t>(stream), err, d_rgba_f32, d_rgba_u8, n_pixels);
 }
 
 }  // namespace mp

@@ -202,8 +202,10 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
 
 int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixels, void* stream, std::string& err);
 
-// Launch record (mp_ctx_last_kernels): the launchers above note every kernel they launch, by name, in a list of the calling thread.
-// launch_log_clear() empties it; launch_log_text() gives the distinct names since then, in launch order, one per line.
+// The launchers above decide nothing themselves: each asks its plan (launch_plan.h: kernel id, grid, LDS, refusals), fills the
+// kernel's parameters and launches the id through the one switch over kernel_table.h.
+// Launch record (mp_ctx_last_kernels): that switch notes every kernel it launches in a list of the calling thread.
+// launch_log_clear() empties it; launch_log_text() gives the distinct names (the table's) since then, in launch order, one per line.
 void launch_log_clear();
 std::string launch_log_text();
 

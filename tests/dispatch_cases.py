@@ -1,27 +1,54 @@
-"""The dispatch census: one parity case per kernel instantiation that minipath_amd/csrc/kernels.hip can launch, keyed by the name
-mp_ctx_last_kernels reports (the kernel with its template arguments as the launch site writes them).  Plain data, importable
-without a GPU: tests/test_dispatch_census_cpu.py asserts that the keys are exactly the launch sites of kernels.hip, and
-tests/test_gpu_dispatch_matrix.py runs every row on the GPU against the oracle.
+"""The dispatch census: one parity case per kernel instantiation of minipath_amd/csrc/kernel_table.h, keyed by the name
+mp_ctx_last_kernels reports (the kernel with its template arguments as the table's row writes them).  Plain data, importable
+without a GPU: tests/test_dispatch_census_cpu.py asserts that the keys are exactly the table's rows, tests/test_launch_plan_cpu.py
+sends every row through the launch plans (launch_plan.cpp) and must get the row's name, and tests/test_gpu_dispatch_matrix.py runs
+every row on the GPU against the oracle.
 
 A row: api    "render" (reference semantics), "paths" (MP_FLAG_PATHS), "wf" (+ MP_FLAG_WAVEFRONT), "aov" (feature planes),
               "trace" / "bounded" / "occluded" (ray queries), "rays" (mp_generate_rays), "untile", "async" (mp.render)
        scene  "teapot", "atrium" (scenes.atrium(1, 0.08): traversal arrays over 1 MB, stack bound 34), "group" ({teapot, soup,
               sphere}), "sphere", "atrium*2^27" (the atrium scaled until its coordinates pass the triangle masks' 2^30 bound);
-              "+rgb" = under a coloured / checker material table
+              "+rgb" = under a coloured / checker material table.  FACTS holds what a launch plan reads off each scene.
        spp    samples per pixel (= samples of the pass)
        opts   the five launch options, every one set explicitly by every case (DEFAULTS, then the row's)
        also   other names the same call must report besides the row's key (the staged pipeline's stages, the async worker's render)
 
-Why each row selects its kernel follows launch_render_tiles / launch_render_aov / launch_render_paths_wavefront as they stand;
-the frames of the matrix (72 x 40 and smaller) are all "small launches" there (units * 16 < CUs * 32 * 24), so 32 or more
-samples select 32 in flight.  So the 32-in-flight forms, <32, *, 8> included, are pinned through that rule; the launcher's other
-two ways to them (`big && nspp >= 128`, and the cached table of a launch that is not small) need frames of 12 288 work units
-or more, whose oracle renders do not fit a test: those two selection rules are not exercised by name."""
+Why each row selects its kernel follows plan_render_tiles / plan_render_aov / plan_render_paths_wavefront as they stand; the
+frames of the matrix (72 x 40 and smaller) are all "small launches" there (units * 16 < CUs * 32 * 24), so 32 or more samples
+select 32 in flight.  On the GPU the 32-in-flight forms, <32, *, 8> included, are reached through that rule.  The plans' other
+two ways to them (`big && nspp >= 128`, and the cached table of a launch that is not small) need frames of 12 288 work units or
+more, whose oracle renders do not fit a test; tests/test_launch_plan_cpu.py pins both by name on the benchmark's own frame."""
 
 DEFAULTS = {"packet_samples_in_flight": 0, "packet_mask_cache": 1, "packet_stack_registers": 64, "packet_rays_per_lane": 1, "paths_pooled": 1}
+# the frames of the matrix: render / path / staged cases 3 x 2 tiles with the right column and bottom row clipped; the feature planes'
+# model costs one ctypes call per ray; path cases bounce (max_depth >= 2); ray queries
+RES, TS = (72, 40), 32
+AOV_RES, AOV_TS = (24, 16), 16
+DEPTH = 3
+N_RAYS = 6000
 LDS_REGS = {"teapot": 3, "group": 3, "atrium": 8}  # packet_stack_registers below the scene's stack bound (22, 22, 34)
 
-# kernels.hip launches these too, but they are utilities, not instantiations of the render / query paths: no row
+# What a launch plan reads off a scene (DevScene): kind 0 TriangleBvh / object group, 1 Sphere; the traversal-stack bound; nodes of
+# the wide tree and packets (an object group has no arrays of its own: 0, its members are walked one by one); whether the triangle
+# masks' coordinate bound holds and every child box is ordered; the members of a group.  test_gpu_dispatch_matrix.py asserts that
+# the live scenes report the same stack bound, node and packet counts; tris_bounded and boxes_ordered are not reported by the API
+# and are held by the kernel names of the rows that read them (the cached rows and the gate "triangle coordinates beyond 2^30").
+FACTS = {
+    "teapot": {"kind": 0, "stack_bound": 22, "nodes": 27, "packets": 319, "tris_bounded": 1, "boxes_ordered": 1, "members": 0},
+    "atrium": {"kind": 0, "stack_bound": 34, "nodes": 214, "packets": 2898, "tris_bounded": 1, "boxes_ordered": 1, "members": 0},
+    "atrium*2^27": {"kind": 0, "stack_bound": 34, "nodes": 214, "packets": 2898, "tris_bounded": 0, "boxes_ordered": 1, "members": 0},
+    "group": {"kind": 0, "stack_bound": 22, "nodes": 0, "packets": 0, "tris_bounded": 0, "boxes_ordered": 0, "members": 3},
+    "sphere": {"kind": 1, "stack_bound": 1, "nodes": 0, "packets": 0, "tris_bounded": 0, "boxes_ordered": 0, "members": 0},
+}
+
+
+def scene_facts(key):
+    """FACTS of a row's scene, "+rgb" = a coloured table"""
+    base, _, rgb = key.partition("+")
+    return {**FACTS[base], "rgb": 1 if rgb else 0}
+
+
+# the table holds these too, but they are utilities, not instantiations of the render / query paths: no row
 EXCLUDED = {
     "set_u64_kernel": "one-thread store that initialises the ray-segment counter; its value is asserted by every counted case",
 }

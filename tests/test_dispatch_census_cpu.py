@@ -1,15 +1,19 @@
-"""The dispatch census (no GPU): every kernel launch of minipath_amd/csrc/kernels.hip goes through the recording macro MP_LAUNCH, and
-the set of instantiation names those sites can launch -- read from the source, the small launch macros expanded -- is exactly the
-set of rows of tests/dispatch_cases.py, which tests/test_gpu_dispatch_matrix.py runs one by one.  A new instantiation without a
-parity case, or a case whose instantiation is gone, fails here, on every machine."""
+"""The dispatch census (no GPU): the kernel table (minipath_amd/csrc/kernel_table.h, read from the built probe libmp_plan_probe.so) is
+exactly the set of rows of tests/dispatch_cases.py, which tests/test_gpu_dispatch_matrix.py runs one by one; kernels.hip launches in
+one place only, the switch the table generates, which records the row's name; and no instantiation of a kernel template is named
+outside the table.  A new instantiation without a parity case, or a case whose instantiation is gone, fails here, on every machine."""
+import ctypes as C
 import os
 import re
-
+import shutil
+import subprocess
 
 from tests import dispatch_cases as dc
+from tests import plan_probe as pp
 from tests.conftest import ROOT
 
 CSRC = os.path.join(ROOT, "minipath_amd", "csrc")
+RAW_LAUNCH = r"\bhipLaunchKernelGGL\b|<<<|\bhipLaunchKernel\b|\bhipModuleLaunchKernel\b|\bhipExtLaunchKernelGGL\b"
 
 
 def _strip_comments(text):
@@ -17,120 +21,59 @@ def _strip_comments(text):
     return re.sub(r"//[^\n]*", "", text)
 
 
-def _call_args(text, pos):
-    """the top-level, comma-separated arguments of the call whose '(' is at pos, and the index after its ')'"""
-    assert text[pos] == "("
-    depth, args, cur, i = 0, [], "", pos
-    while True:
-        ch = text[i]
-        if ch in "([{":
-            depth += 1
-        elif ch in ")]}":
-            depth -= 1
-            if depth == 0:
-                args.append(cur.strip())
-                return args, i + 1
-        if ch == "," and depth == 1:
-            args.append(cur.strip())
-            cur = ""
-        elif not (depth == 1 and ch == "(" and i == pos):
-            cur += ch
-        i += 1
+def _library_sources():
+    return {f: _strip_comments(open(os.path.join(CSRC, f)).read()) for f in sorted(os.listdir(CSRC))
+            if f.endswith((".cpp", ".h", ".hip")) and f not in dc.PROBE_FILES}
 
 
-def _defines(text):
-    """{name: (params or None, body)} of the #define lines, continuation lines joined"""
-    out = {}
-    joined = re.sub(r"\\\n", " ", text)
-    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(\w+)(\(([^)]*)\))?[ \t]*(.*)$", joined, flags=re.M):
-        params = [p.strip() for p in m.group(3).split(",")] if m.group(2) else None
-        out.setdefault(m.group(1), (params, m.group(4).strip()))
-    return out
+def census(names):
+    """what separates a kernel table from the case table: (instantiations without a case, cases without an instantiation)"""
+    assert len(names) == len(set(names)), "no instantiation has two rows"
+    for name, why in dc.EXCLUDED.items():
+        assert name in names and why, f"{name} is excluded but no longer in the table"
+    table, cases = set(names) - set(dc.EXCLUDED), set(dc.CASES)
+    return sorted(table - cases), sorted(cases - table)
 
 
-def _normal(name):
-    """the preprocessor's stringification of the kernel argument, as launch_log_text() reports it"""
-    name = re.sub(r"\s+", " ", name.strip())
-    if name.startswith("(") and name.endswith(")"):
-        name = name[1:-1].strip()
-    return re.sub(r"\s*,\s*", ", ", name)
-
-
-def launch_sites(path):
-    return launch_sites_of(open(path).read())
-
-
-def launch_sites_of(source):
-    """Names of every kernel the source launches through MP_LAUNCH, its launch macros (macros whose body launches) expanded at their
-    uses and object-like macros inside the template arguments (MP_MCACHE_WPE) replaced by their default."""
-    text = _strip_comments(source)
-    defs = _defines(text)
-    launchers = {n: d for n, d in defs.items() if n != "MP_LAUNCH" and d[0] is not None and "MP_LAUNCH(" in d[1]}
-    consts = {n: d[1] for n, d in defs.items() if d[0] is None and re.fullmatch(r"\d+", d[1] or "")}
-    body = re.sub(r"\\\n", " ", text)
-    body = re.sub(r"^[ \t]*#[ \t]*define[^\n]*$", "", body, flags=re.M)  # uses only: the definitions were read above
-    for _ in range(4):  # launch macros do not nest deeper
-        for name, (params, mbody) in launchers.items():
-            while True:
-                m = re.search(r"\b%s\(" % name, body)
-                if not m:
-                    break
-                args, end = _call_args(body, m.end() - 1)
-                if params and params[-1] == "...":
-                    fixed = params[:-1]
-                    args = args[:len(fixed)] + [", ".join(args[len(fixed):])]
-                    names = fixed + ["__VA_ARGS__"]
-                else:
-                    names = params
-                assert len(args) == len(names), (name, args)
-                exp = mbody
-                for p, a in zip(names, args):
-                    exp = re.sub(r"\b%s\b" % p, a, exp)
-                body = body[:m.start()] + exp + body[end:]
-    names = []
-    for m in re.finditer(r"\bMP_LAUNCH\(", body):
-        args, _ = _call_args(body, m.end() - 1)
-        k = args[0]
-        for c, v in consts.items():
-            k = re.sub(r"\b%s\b" % c, v, k)
-        names.append(_normal(k))
-    return names
+def test_the_case_table_is_the_census():
+    assert census(pp.table()) == ([], [])
+    # the names are the rows as written, the MP_MCACHE_WPE position at its default
+    for n in ("render_tiles_packet_kernel<16, true, 7>", "render_tiles_packet_kernel<32, false, 8, false, true>", "render_paths_kernel<2, true, false>",
+              "render_aov_packet_kernel<16, false, 8, false, true>", "query_rays_kernel<true, kAnyHit>", "wf_scan_kernel"):
+        assert n in pp.table(), n
+    assert not [n for n in pp.table() if "MP_" in n or "  " in n]
 
 
 def test_no_launch_bypasses_the_record():
-    text = _strip_comments(open(os.path.join(CSRC, "kernels.hip")).read())
-    raw = [m.start() for m in re.finditer(r"\bhipLaunchKernelGGL\b|<<<|\bhipLaunchKernel\b|\bhipModuleLaunchKernel\b|\bhipExtLaunchKernelGGL\b", text)]
+    src = _library_sources()
+    text = src["kernels.hip"]
+    raw = [m.start() for m in re.finditer(RAW_LAUNCH, text)]
     assert len(raw) == 1, "kernels.hip launches only inside the MP_LAUNCH macro"
     line = text[: raw[0]].count("\n")
-    window = "\n".join(text.split("\n")[line - 4: line + 1])
-    assert "#define MP_LAUNCH(" in window and "note_launch(MP_STR(kernel))" in window, "the one raw launch is MP_LAUNCH's own, next to its record"
+    window = "\n".join(text.split("\n")[line - 3: line + 1])
+    assert "#define MP_LAUNCH(" in window and "note_launch(id)" in window, "the one raw launch is MP_LAUNCH's own, next to its record"
+    uses = [m.start() for m in re.finditer(r"\bMP_LAUNCH\(", text) if "#define" not in text[text.rfind("\n", 0, m.start()):m.start()]]
+    assert len(uses) == 1, "MP_LAUNCH is used once: by the switch over the table"
+    at = text[: uses[0]].count("\n")
+    around = "\n".join(text.split("\n")[at - 3: at + 6])
+    assert "#define MP_X(row, ...)" in around and "case row:" in around and "MP_KERNEL_TABLE(MP_X)" in around, "... generated from the table, row by row"
     # the other sources of the library launch nothing
-    for f in sorted(os.listdir(CSRC)):
-        if f.endswith((".cpp", ".h", ".hip")) and f != "kernels.hip" and f not in dc.PROBE_FILES:
-            t = _strip_comments(open(os.path.join(CSRC, f)).read())
-            assert not re.search(r"\bhipLaunchKernelGGL\b|<<<|\bMP_LAUNCH\(", t), f
+    for f, t in src.items():
+        if f != "kernels.hip":
+            assert not re.search(RAW_LAUNCH + r"|\bMP_LAUNCH\(", t), f
     for f in dc.PROBE_FILES:
         assert os.path.exists(os.path.join(CSRC, f)), f"{f} is excluded but gone"
 
 
-def test_the_case_table_is_the_census():
-    sites = launch_sites(os.path.join(CSRC, "kernels.hip"))
-    assert len(sites) == len(set(sites)), "no instantiation is launched from two sites"
-    parsed = set(sites)
-    for name, why in dc.EXCLUDED.items():
-        assert name in parsed and why, f"{name} is excluded but no longer launched"
-    census = parsed - set(dc.EXCLUDED)
-    table = set(dc.CASES)
-    assert table == census, {"instantiations without a case": sorted(census - table), "cases without an instantiation": sorted(table - census)}
-
-
-def test_the_parser_sees_what_the_preprocessor_sees():
-    """spot checks of the expansion: nested launch macros, variadic template arguments, an object-like macro in the arguments"""
-    sites = set(launch_sites(os.path.join(CSRC, "kernels.hip")))
-    for n in ("render_tiles_packet_kernel<16, true, 7>", "render_tiles_packet_kernel<32, false, 8, false, true>", "render_paths_kernel<2, true, false>",
-              "render_aov_packet_kernel<16, false, 8, false, true>", "query_rays_kernel<true, kAnyHit>", "wf_scan_kernel"):
-        assert n in sites, n
-    assert not [n for n in sites if "SV" in n or "__VA_ARGS__" in n or "MP_" in n]
+def test_kernel_templates_are_instantiated_by_the_table_alone():
+    src = _library_sources()
+    templates = set(re.findall(r"^template <[^\n]*>\n__global__ [^\n]*\bvoid (\w+)\(", src["kernels.hip"], flags=re.M))
+    assert {"render_tiles_packet_kernel", "render_paths_kernel", "render_aov_packet_kernel", "wf_camera_kernel", "query_rays_kernel"} <= templates
+    assert {n.split("<")[0] for n in pp.table() if "<" in n} == templates, "every kernel template has rows, and only kernel templates have arguments"
+    for f, t in src.items():
+        if f != "kernel_table.h":
+            named = [k for k in templates if re.search(r"\b%s\s*<" % k, t)]
+            assert not named, (f, named)
 
 
 def test_rows_are_well_formed():
@@ -138,6 +81,7 @@ def test_rows_are_well_formed():
     for name, row in rows:
         assert set(row["opts"]) <= set(dc.DEFAULTS), name
         assert row["api"] in ("render", "paths", "wf", "aov", "trace", "bounded", "occluded", "rays", "untile", "async")
+        assert row["scene"].partition("+")[0] in dc.FACTS, name
         for other in row["also"]:
             assert other in dc.CASES, (name, other)
     for expected, _ in dc.GATES.values():
@@ -147,15 +91,33 @@ def test_rows_are_well_formed():
         assert all(k in dc.CASES for _, k in passes)
 
 
-def test_a_changed_launcher_is_noticed():
-    """the parser on edited copies of the source: a new site written plainly, a new use of a launch macro, a site taken out"""
-    src = open(os.path.join(CSRC, "kernels.hip")).read()
-    census = set(launch_sites_of(src))
-    at = "    else MP_LAUNCH_PACKET(1, 7);\n"
-    assert src.count(at) == 1
-    plain = src.replace(at, at + "    MP_LAUNCH((render_tiles_packet_kernel<128, false, 7>), dim3(grid), dim3(256), 0, st, P);\n")
-    assert set(launch_sites_of(plain)) - census == {"render_tiles_packet_kernel<128, false, 7>"}
-    macro = src.replace(at, at + "    MP_LAUNCH_PACKET(128, 5);\n")
-    assert set(launch_sites_of(macro)) - census == {"render_tiles_packet_kernel<128, true, 5>", "render_tiles_packet_kernel<128, false, 5>"}
-    gone = src.replace("MP_LAUNCH(wf_scan_kernel,", "launch_elsewhere(wf_scan_kernel,")
-    assert census - set(launch_sites_of(gone)) == {"wf_scan_kernel"}
+def _table_of(tmp_path, tag, edit):
+    """the names of a probe built from a copy of the sources whose kernel_table.h went through edit()"""
+    inc, work = tmp_path / tag / "include", tmp_path / tag / "pkg" / "csrc"  # mp_internal.h includes ../../include/minipath_hip.h
+    inc.mkdir(parents=True)
+    work.mkdir(parents=True)
+    shutil.copy(os.path.join(ROOT, "include", "minipath_hip.h"), inc)
+    for f in ("launch_plan.cpp", "launch_plan.h", "plan_probe.cpp", "mp_internal.h", "kernel_table.h"):
+        shutil.copy(os.path.join(CSRC, f), work)
+    table = work / "kernel_table.h"
+    before = table.read_text()
+    after = edit(before)
+    assert after != before
+    table.write_text(after)
+    cxx = os.environ.get("HOSTCXX") or next(c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++"), shutil.which("c++")) if c and os.path.exists(c))
+    so = str(work / "probe.so")
+    subprocess.run([cxx, "-O0", "-std=c++17", "-fPIC", "-shared", "-o", so, "plan_probe.cpp", "launch_plan.cpp"], cwd=work, check=True)
+    L = C.CDLL(so)
+    L.mp_plan_kernel_name.restype = C.c_char_p
+    return [L.mp_plan_kernel_name(i).decode() for i in range(L.mp_plan_kernel_count())]
+
+
+def test_a_changed_launcher_is_noticed(tmp_path):
+    """the census on probes built from edited copies of the list: a row added, a row taken out"""
+    at = "    X(K_PACKET_1,              render_tiles_packet_kernel<1, false, 7>)                             \\\n"
+    added = _table_of(tmp_path, "added", lambda s: s.replace(at, at + "    X(K_PACKET_128, render_tiles_packet_kernel<128, false, 7>) \\\n"))
+    assert census(added) == (["render_tiles_packet_kernel<128, false, 7>"], [])
+    row = "    X(K_QUANTISE,              quantise_kernel)\n"
+    gone = _table_of(tmp_path, "gone", lambda s: s.replace("untile_kernel)                                                       \\\n" + row,
+                                                           "untile_kernel)\n"))
+    assert census(gone) == ([], ["quantise_kernel"])

@@ -1,4 +1,4 @@
-"""GPU dispatch matrix (-m gpu): one case per kernel instantiation of tests/dispatch_cases.py (= every launch site of kernels.hip, see
+"""GPU dispatch matrix (-m gpu): one case per kernel instantiation of tests/dispatch_cases.py (= every row of kernel_table.h, see
 tests/test_dispatch_census_cpu.py).  Each case builds the smallest input that selects its instantiation, runs it through the
 public API, asserts that mp_ctx_last_kernels names exactly that instantiation, and compares the result bit for bit with the
 oracle's for the same input (never with another GPU run).  Then the gate cases -- the mask cache's guards must send a frame to the
@@ -21,9 +21,7 @@ F = np.float32
 NO = 0xFFFFFFFF
 FMAX = np.finfo(np.float32).max
 SEED = 0x5EED
-RES, TS = (72, 40), 32       # frames of the render / path / staged cases: 3 x 2 tiles, the right column and bottom row clipped
-AOV_RES, AOV_TS = (24, 16), 16  # the feature planes' model costs one ctypes call per ray
-DEPTH = 3                    # path cases: max_depth >= 2, so that paths bounce
+RES, TS, AOV_RES, AOV_TS, DEPTH = dc.RES, dc.TS, dc.AOV_RES, dc.AOV_TS, dc.DEPTH  # the frames the CPU plan tests size the same rows with
 GREY = [(0.8, 0.0), (0.2, 2.5), (0.6, 0.0)]
 RGB = [{"albedo": (0.9, 0.85, 0.8), "albedo2": (0.1, 0.15, 0.7), "checker": 6.0}, ((0.7, 0.2, 0.3), (0.0, 0.0, 0.0)),
        {"albedo": 0.4, "emission": (1.5, 0.5, 0.0), "albedo2": (0.2, 0.9, 0.2), "checker": 0.75}]
@@ -239,7 +237,7 @@ def _queries(world, name, row):
 
     s = world.scene(row["scene"])
     gpu, info = s["gpu"], s["gpu"].info()
-    o, d = meshes.random_rays(6000, 23, np.array(list(info.bbox_min), F), np.array(list(info.bbox_max), F))
+    o, d = meshes.random_rays(dc.N_RAYS, 23, np.array(list(info.bbox_min), F), np.array(list(info.bbox_max), F))
     t, prim, u, v, inst = s["orc"].trace_inst(o, d) if s["group"] else (*s["orc"].trace(o, d), np.zeros(o.shape[0], np.uint32))
     hit = prim != NO
     assert 0 < hit.sum() < hit.size, "hits and misses"
@@ -328,6 +326,27 @@ def _async(world, name, row):
     assert world.kernels() == list(row["also"]) + [name]  # every batch: the render kernel, then color_to_image on the device
     assert np.array_equal(bits(job.image_f32()), bits(of)) and np.array_equal(job.image(), ou8)
     job.close()
+
+
+@pytest.mark.parametrize("key", list(dc.FACTS))
+def test_scene_facts(world, key):
+    """The live scene reports what dispatch_cases.FACTS records for it, so that the CPU plan tests size and select with the
+    GPU's own numbers.  (tris_bounded / boxes_ordered are not reported: the kernel names of the cached rows and of the gate
+    "triangle coordinates beyond 2^30" hold them.)"""
+    want, s = dc.FACTS[key], world.scene(key)
+    gpu, info = s["gpu"], s["gpu"].info()
+    assert info.stack_bound == want["stack_bound"]
+    assert ("sphere" in s) == (want["kind"] == 1) and s["group"] == (want["members"] != 0)
+    if s["group"]:
+        assert len(s["keep"][0]) == want["members"]
+        assert info.stack_bound == max(m.info().stack_bound for m in s["keep"][0])
+    if want["kind"] == 0 and not s["group"]:  # a tree of its own: the wide tree's nodes, the packets
+        nodes = gpu.device_tree()[0]
+        assert (len(nodes), info.packet_count) == (want["nodes"], want["packets"])
+    else:  # no arrays of its own: the plans read 0 and 0
+        assert (want["nodes"], want["packets"]) == (0, 0)
+        with pytest.raises(mp.MinipathError):
+            gpu.device_tree()
 
 
 @pytest.mark.parametrize("name", list(dc.CASES))
