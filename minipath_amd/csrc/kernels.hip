@@ -95,29 +95,17 @@ struct RayGen {
     uint64_t seed;  // mix(settings.seed), see mixed_seed()
 };
 
-// geometry/mod.rs:45-54 (the short division / sqrt sequences where they are exact: ray_math.h)
-__device__ __forceinline__ void ray_new(float ox, float oy, float oz, float dx, float dy, float dz, Ray& r) {
-    r.ox = ox; r.oy = oy; r.oz = oz;
-    rm::ray_dir(dx, dy, dz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
-}
-
-// CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream (ADVANCE = false: nothing is drawn from it afterwards)
+// CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream (ADVANCE = false: nothing is drawn from it afterwards);
+// ray_new and the arithmetic from the film point on are camera_rays.h's (camera_film, camera_lens_ray): the mask cache's corner rays share it
 template <bool ADVANCE = true>
 __device__ __forceinline__ void sample_ray_rng(const RayGen& P, uint32_t x, uint32_t y, Rng& rng, Ray& r) {
     float film_u = static_cast<float>(x) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
     float film_v = static_cast<float>(y) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
-    float fv = film_v * P.s.pixel_scale, fu = film_u * P.s.pixel_scale;
-    float fx = P.s.film_origin_offset[0] + P.s.up[0] * fv - P.s.right[0] * fu;
-    float fy = P.s.film_origin_offset[1] + P.s.up[1] * fv - P.s.right[1] * fu;
-    float fz = P.s.film_origin_offset[2] + P.s.up[2] * fv - P.s.right[2] * fu;
+    float f[3];
+    camera_film(P.s, film_u, film_v, f);
     float x1, x2;
     unit_disc<ADVANCE>(rng, x1, x2);
-    float a = P.s.lens_radius * x1, b = P.s.lens_radius * x2;
-    float lx = P.s.right[0] * a + P.s.up[0] * b;
-    float ly = P.s.right[1] * a + P.s.up[1] * b;
-    float lz = P.s.right[2] * a + P.s.up[2] * b;
-    ray_new(P.s.center[0] + lx, P.s.center[1] + ly, P.s.center[2] + lz, lx * P.s.lens_weight - fx,
-            ly * P.s.lens_weight - fy, lz * P.s.lens_weight - fz, r);
+    camera_lens_ray(P.s, f, x1, x2, r);
 }
 
 // key = mix(seed) + sample index; `P.seed` already holds mix(seed) (mixed_seed(), on the host)
@@ -1488,9 +1476,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
         const size_t off = (static_cast<size_t>(tile_i) * ts * ts + static_cast<size_t>(py - T.min_y) * ts + (px - T.min_x)) * 4;
         float acc, cnt;  // pixel_sum (r=g=b) and alpha (worker.rs:40)
         pixel_state_load(P, off, inpix, sub == 0, acc, cnt);
-        if (MCACHE) {  // a new unit: other pixels, other bounds
-            if (lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;
-            wave_lds_sync();
+        if (MCACHE) {  // a new unit: other pixels, other bounds, set from the camera
+            const RenderParams& C = params_view(KP);  // corner rays
+            const uint32_t ux = T.min_x + (b % bx) * BW, uy = T.min_y + (b / bx) * BH;
+            mask_cache_begin_unit(mc, C.gen.s, C.gen.jitter_scale, ux, min(ux + BW, T.max_x) - 1u, uy, min(uy + BH, T.max_y) - 1u);
         }
         // passes are aligned to multiples of S in the absolute sample index, so that a chunk boundary (MP_FLAG_CHUNKED_SUM) never
         // falls inside a pass; lanes outside [s_begin, s_end) add +0.0, which is exact

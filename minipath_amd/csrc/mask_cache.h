@@ -2,7 +2,7 @@
 // prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
 // that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
 // per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define
-// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_NODE_ENTRIES / MP_LEAF_ENTRIES before including it.
+// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES before including it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,8 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+
+#include "camera_rays.h"
 
 #ifndef MP_PROF_COUNT
 #define MP_PROF_COUNT(i) do { } while (0)
@@ -75,8 +77,9 @@ __device__ __forceinline__ void slab(float bnx, float bny, float bnz, float bxx,
 // contains every pass's rays gives one 8-bit "children that may be hit" mask per node, cached in LDS (the packet kernel uses no
 // other LDS).  Every pass checks, lane by lane, that its ray lies inside B (no reduction), and while that holds and the sign
 // pattern is the same, a node visit costs one LDS lookup and the exact per-ray slab tests of the surviving children only.  B starts
-// as the bounds of the first pass (wave reductions) widened by MP_MCACHE_PAD of their extent; a pass that does not fit widens B and
-// clears the cache.
+// as the bounds of the unit's corner rays, computed from the camera (mask_cache_begin_unit), or, where that declines, as the bounds
+// of the first pass (wave reductions) widened by MP_MCACHE_PAD of their extent; a pass that does not fit widens B and clears the
+// cache.
 // Why skipping a child whose bit is clear is exact.  Only in the sign-specialised walks (OCT >= 0: every active ray has finite
 // inverse directions of one sign pattern) and only if every active origin and inverse component is finite.  Axis with inv > 0
 // (aabb.rs:257-271 gives lo = fl(fl(bmin - o) * inv), hi = fl(fl(bmax - o) * inv)): with omax >= o for every ray,
@@ -223,6 +226,73 @@ __device__ __forceinline__ void mask_cache_begin_pass(const MaskCache& mc, const
         for (int i = 0; i < (kMaskCacheEntries + kLeafCacheEntries) / 64; i++) mc.lds[kMaskCacheHeader + i * 64 + l_] = 0xFFFFFFFFu;  // no node / leaf has this tag
         wave_lds_sync();
     }
+}
+// ---- B from the camera: the unit's bounds before its first pass ------------------------------------------------------------------
+// A unit's rays are a closed-form function of the camera (camera_rays.h): film points inside its pixel block (widened by the jitter) and lens points
+// inside the lens disc.  Origins and unnormalised directions are linear in (film_u, film_v, lens a, lens b), so over the box
+// [u0, u1] x [v0, v1] x [-lens_radius, lens_radius]^2 their extremes sit at its 16 corners; a normalised direction component is not
+// monotone in the other two, so its extreme can lie off a corner by a term of second order in the footprint's angle, which
+// MP_MCACHE_MARGIN covers (counted: profiles/analytic_bounds_notes.md).  B is a guess that every pass verifies
+// (mask_cache_begin_pass): a ray outside it costs a widen-and-clear, never a result.
+#ifndef MP_MCACHE_MARGIN
+#define MP_MCACHE_MARGIN 0.015625f  // widening of the corner rays' bounds on either side, in their own extents (A/B: 1/64 .. 1/8, profiles/analytic_bounds_notes.md)
+#endif
+// Called once per work unit, by every lane of the wave, before the unit's first pass.  The unit's pixels are [x0, x1] x [y0, y1]
+// (inclusive) and a sample's film point is pixel + (u * jitter_scale - 0.5) with u in [0, 1).  Lane l builds corner l & 15 (bit 0:
+// film_u high, bit 1: film_v high, bit 2 / 3: lens a / b high; the four copies of a corner reduce like one).  If every corner may
+// use the cached walk and their inverse directions share one sign pattern, B = the corners' bounds widened by MP_MCACHE_MARGIN of
+// their extent under the guards of mask_cache_begin_pass, and the node and leaf tags are cleared (the clear the first pass's set
+// would do).  Otherwise no B: the first pass sets it by reduction, as it does for a pass of another sign pattern.
+__device__ __forceinline__ void mask_cache_begin_unit(const MaskCache& mc, const mp_camera_sampler& s, float jitter_scale, uint32_t x0,
+                                                      uint32_t x1, uint32_t y0, uint32_t y1) {
+    const int lane = static_cast<int>(threadIdx.x) & 63;
+    Ray r;
+    float f[3];
+    camera_film(s, (lane & 1) ? static_cast<float>(x1) + (jitter_scale + (-0.5f)) : static_cast<float>(x0) + (-0.5f),
+                (lane & 2) ? static_cast<float>(y1) + (jitter_scale + (-0.5f)) : static_cast<float>(y0) + (-0.5f), f);
+    camera_lens_ray(s, f, (lane & 4) ? 1.0f : -1.0f, (lane & 8) ? 1.0f : -1.0f, r);
+    const uint64_t nx = __ballot(r.ix < 0.0f), ny = __ballot(r.iy < 0.0f), nz = __ballot(r.iz < 0.0f);
+    const bool adopt = __ballot(!mask_cache_ray_ok(r)) == 0 && (nx == 0 || ~nx == 0) && (ny == 0 || ~ny == 0) && (nz == 0 || ~nz == 0);
+    if (!adopt) {
+        if (lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;
+        wave_lds_sync();
+        return;
+    }
+    const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+    float pmin[3][3] = {{r.ox, r.oy, r.oz}, {r.ix, r.iy, r.iz}, {r.dx, r.dy, r.dz}}, pmax[3][3];  // after the reductions: lane 63 holds the bounds
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) pmax[g][k] = pmin[g][k];
+        wave_min3_max3(pmin[g], pmax[g]);
+    }
+    float* hdr = reinterpret_cast<float*>(mc.lds);
+    if (lane == 63) {
+#pragma unroll
+        for (int g = 0; g < 3; g++) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {  // mask_cache_begin_pass's widening, with the margin for the pad
+                const float lo = pmin[g][k], hi = pmax[g][k];
+                const float pad = (hi - lo) * MP_MCACHE_MARGIN;
+                float wlo = lo - pad, whi = hi + pad;
+                if (g == 1) {
+                    if ((wlo < 0.0f) != (lo < 0.0f) || wlo == 0.0f) wlo = lo;
+                    if ((whi < 0.0f) != (hi < 0.0f) || whi == 0.0f) whi = hi;
+                    if (!(fabsf(wlo) < INFINITY)) wlo = lo;
+                    if (!(fabsf(whi) < INFINITY)) whi = hi;
+                } else {
+                    const float cap = g == 0 ? 2.0f * kCoordCap : 2.0f;
+                    wlo = fmaxf(wlo, -cap); whi = fminf(whi, cap);
+                }
+                hdr[hdr_lo(g) + k] = wlo; hdr[hdr_lo(g) + 3 + k] = whi;
+            }
+        }
+        mc.lds[kHdrState] = oct | 0x100u;
+    }
+    MP_PROF_COUNT(3);
+#pragma unroll
+    for (int i = 0; i < (kMaskCacheEntries + kLeafCacheEntries) / 64; i++) mc.lds[kMaskCacheHeader + i * 64 + lane] = 0xFFFFFFFFu;  // no node / leaf has this tag
+    wave_lds_sync();
 }
 // lane j (0..7): can any ray with origin / inverse direction inside the bounds `b` (omin[3], omax[3], imin[3], imax[3]) pass child
 // j's box {bmn, bmx}?  (see above)

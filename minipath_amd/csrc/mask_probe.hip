@@ -5,7 +5,8 @@
 //   * bounds_may_hit<OCT> against slab<false, OCT> (aabb.rs:254-284, limit FLT_MAX) of 192 rays inside B, all eight patterns;
 //   * mask_cache_ray_ok against its plain definition, every f32 bit pattern in each of the nine components;
 //   * bounds_deviation against `v < lo || v > hi`;
-//   * mask_cache_begin_pass against a serial restatement of its rule, over sequences of passes per wave.
+//   * mask_cache_begin_pass against a serial restatement of its rule, over sequences of passes per wave;
+//   * mask_cache_begin_unit's header for given cameras and pixel blocks, handed back for the host model of the test.
 // The 192 rays of a case are the 64 corners of its 6-D box (origin x direction or origin x inverse direction), those corners moved
 // one ulp inward in every coordinate, and 64 interior points (one in four snapped onto a face); one wave per case, lane l owns rays
 // l, 64 + l and 128 + l.  Counters (unsigned long long out[8]): [0] violations, [1] cases, [2] smallest violating case index (~0 if
@@ -595,6 +596,31 @@ __global__ void __launch_bounds__(256) pass_kernel(uint64_t seed, unsigned long 
     }
 }
 
+// ---- (e) mask_cache_begin_unit ------------------------------------------------------------------------------------------------------
+// One wave per pixel block {x0, x1, y0, y1}: the header starts as garbage and every node / leaf tag as its own index (never
+// 0xFFFFFFFF); out[20 * unit ..] = header dwords 0..18 after the call, then the number of tags that read 0xFFFFFFFF.
+constexpr int kUnitOut = 20;
+struct SamplerArg {
+    mp_camera_sampler s;
+};
+__global__ void __launch_bounds__(256) unit_kernel(SamplerArg cam, float jitter_scale, const uint32_t* blocks, uint32_t n, uint32_t* out) {
+    __shared__ __align__(16) uint32_t lds[4 * kMaskCacheDwords];
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t unit = blockIdx.x * 4u + w;
+    if (unit >= n) return;  // (whole waves)
+    uint32_t* const base = lds + w * kMaskCacheDwords;
+    if (lane < static_cast<uint32_t>(kMaskCacheHeader)) base[lane] = static_cast<uint32_t>(hsh(0x0E17ull, unit, lane));
+    constexpr int kTags = kLeafMaskBase - kMaskCacheHeader;
+    for (int i = 0; i < kTags / 64; i++) base[kMaskCacheHeader + i * 64 + static_cast<int>(lane)] = static_cast<uint32_t>(i * 64) + lane;
+    wave_lds_sync();
+    mask_cache_begin_unit(MaskCache{base}, cam.s, jitter_scale, blocks[4 * unit], blocks[4 * unit + 1], blocks[4 * unit + 2], blocks[4 * unit + 3]);
+    wave_lds_sync();
+    uint32_t cleared = 0u;
+    for (int i = 0; i < kTags / 64; i++) cleared += static_cast<uint32_t>(__popcll(__ballot(base[kMaskCacheHeader + i * 64 + static_cast<int>(lane)] == 0xFFFFFFFFu)));
+    if (lane < 19u) out[kUnitOut * unit + lane] = base[lane];
+    if (lane == 19u) out[kUnitOut * unit + 19u] = cleared;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // One launch on a fresh counter buffer.  HIP's last-error state is per thread and sticky: an error that earlier work of the process
 // left there is not this probe's, so it is cleared before the launch, and every call's own status is checked (probe.hip).
@@ -711,6 +737,32 @@ int mp_mask_probe_dev(uint64_t seed, const float* set, uint32_t n, uint64_t nran
     if (rc != 0) return rc;
     for (int i = 0; i < kCounters; i++) out[i] = acc[i];
     return static_cast<int>(ef);
+}
+// (e) mask_cache_begin_unit: n pixel blocks {x0, x1, y0, y1} (host) under the sampler's 15 floats -> 20 dwords per block (host):
+// the header and the number of cleared tags; *ntags = tags per wave, *margin = the MP_MCACHE_MARGIN the probe was built with
+int mp_mask_probe_unit(const float* sampler, float jitter_scale, const uint32_t* blocks, uint32_t n, uint32_t* out, uint32_t* ntags,
+                       float* margin) {
+    (void)hipGetLastError();
+    *ntags = static_cast<uint32_t>(kLeafMaskBase - kMaskCacheHeader);
+    *margin = MP_MCACHE_MARGIN;
+    if (n == 0u) return 0;
+    SamplerArg cam;
+    const float* p = sampler;
+    for (int k = 0; k < 3; k++) { cam.s.center[k] = p[k]; cam.s.up[k] = p[3 + k]; cam.s.right[k] = p[6 + k]; cam.s.film_origin_offset[k] = p[9 + k]; }
+    cam.s.pixel_scale = p[12]; cam.s.lens_radius = p[13]; cam.s.lens_weight = p[14];
+    uint32_t *dblocks = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc(&dblocks, sizeof(uint32_t) * 4u * n);
+    if (e == hipSuccess) e = hipMalloc(&dout, sizeof(uint32_t) * kUnitOut * n);
+    if (e == hipSuccess) e = hipMemcpy(dblocks, blocks, sizeof(uint32_t) * 4u * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(unit_kernel, dim3((n + 3u) / 4u), dim3(256), 0, 0, cam, jitter_scale, dblocks, n, dout);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(uint32_t) * kUnitOut * n, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(dblocks);
+    (void)hipFree(dout);
+    return static_cast<int>(e);
 }
 // (d) mask_cache_begin_pass: nwaves waves (a multiple of 4) of 64 passes each
 int mp_mask_probe_pass(uint64_t seed, uint64_t nwaves, unsigned long long* out) {
