@@ -78,6 +78,44 @@ def make(name):
     raise KeyError(name)
 
 
+def doubled(name, seed=5, keep=None):
+    """make(name) with every triangle twice: a second copy of the triangle list (same vertex indices, same order) appended and
+    the 2n rows permuted.  Returns (pos, nrm, tex, tri2, copy_id, source): copy_id[i] in {0, 1} = the copy row i came from,
+    source[i] = its triangle of make(name).  Twins share a centroid, so the builder bins them together; where both land in one
+    packet they decode to the same f32 vertices and every ray that hits one hits the other with the same t, u and v, bit for bit.
+    keep = n cuts the mesh down to its first n source triangles before it is doubled (2 n rows)."""
+    pos, nrm, tex, tri = make(name)
+    if keep is not None:
+        tri = tri[:keep]
+    n = tri.shape[0]
+    perm = np.random.default_rng(seed).permutation(2 * n)
+    tri2 = np.ascontiguousarray(np.concatenate([tri, tri])[perm], np.uint32)
+    return pos, nrm, tex, tri2, (perm >= n).astype(np.uint32), (perm % n).astype(np.uint32)
+
+
+STACK_SIZES = (2, 8, 9, 16)
+
+
+def stack(k):
+    """One fixed triangle, oblique to every axis, k times over (k in STACK_SIZES): a whole packet, and a packet plus one, of
+    the same triangle.  Returns (pos, None, None, tri)."""
+    assert k in STACK_SIZES
+    pos = np.array([[-1.25, 0.5, 0.75], [1.5, -0.25, 0.375], [0.125, 1.75, -1.0]], np.float32)
+    return pos, None, None, np.tile(np.arange(3, dtype=np.uint32), (k, 1))
+
+
+def stack_rays(n=32):
+    """n x n parallel rays through stack(k)'s triangle, on a grid over its barycentric square (so about half of them hit, and
+    some run along its edges), from a point off its plane."""
+    pos = stack(2)[0].astype(np.float64)
+    e1, e2 = pos[1] - pos[0], pos[2] - pos[0]
+    a, b = np.meshgrid(np.linspace(0.0, 1.0, n), np.linspace(0.0, 1.0, n), indexing="ij")
+    tgt = pos[0] + a.reshape(-1, 1) * e1 + b.reshape(-1, 1) * e2
+    d = np.cross(e1, e2) + 0.3 * e1 - 0.2 * e2
+    o = tgt - 1.5 * d
+    return o.astype(np.float32), np.tile(d.astype(np.float32), (n * n, 1))
+
+
 def random_rays(n, seed, bmin, bmax):
     """Rays aimed at random points of the (slightly enlarged) box from random outside/inside origins."""
     rng = np.random.default_rng(seed)

@@ -17,6 +17,16 @@ def bits(a): return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 CACHED = len(sys.argv) > 3 and sys.argv[3] == "cached"
 
+def doubled(name, seed=5):
+    """meshes.make(name) with every triangle twice, the 2n rows permuted: (pos, nrm, tex, tri2, copy_id).  Twins that land in one
+    packet tie in t, u and v bit for bit; the lower lane must win.  (The recipe of tests/meshes.py doubled(), written out here so
+    that the tool needs only make(); tests/test_exact_ties_cpu.py holds the two together.)"""
+    pos, nrm, tex, tri = meshes.make(name)
+    n = tri.shape[0]
+    perm = np.random.default_rng(seed).permutation(2 * n)
+    return pos, nrm, tex, np.ascontiguousarray(np.concatenate([tri, tri])[perm], np.uint32), (perm >= n).astype(np.uint32)
+
+
 def run(cases, seed, ctx=None):
     """Returns the number of mismatching cases."""
     rng = np.random.default_rng(seed)
@@ -26,6 +36,9 @@ def run(cases, seed, ctx=None):
         pos, nrm, tex, tri = meshes.make(name)
         mat = (np.arange(tri.shape[0]) * 7 % 3).astype(np.uint32)  # three materials, interleaved
         scenes[name] = (mp.Scene(mp.TriangleBvh.build(pos, nrm, tex, tri, ctx, tri_material=mat)), po.Bvh.build(pos, nrm, tex, tri, tri_material=mat))
+    for name in ("soup_300", "grid_40", "sphere_24", "sliver_fan"):   # every triangle twice: exact ties inside a packet; the copies differ in material
+        pos, nrm, tex, tri, copy_id = doubled(name)
+        scenes[name + "_doubled"] = (mp.Scene(mp.TriangleBvh.build(pos, nrm, tex, tri, ctx, tri_material=copy_id)), po.Bvh.build(pos, nrm, tex, tri, tri_material=copy_id))
     from minipath_amd import scenes as _scenes   # ... and a small stand-in: thin top nodes, absorbed in the wide device tree
     pos, nrm, tex, tri = _scenes.atrium(1, 0.02)
     mat = (np.arange(tri.shape[0]) * 7 % 3).astype(np.uint32)
