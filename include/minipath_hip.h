@@ -220,6 +220,9 @@ int mp_ctx_device(const mp_ctx *ctx, int *device_id, int *cu_count);
  * "multi_gather_staged" (0 default, or 1; read on the gathering context, ctxs[0] of mp_render_frame_multi / mp_render_pass_multi):
  * 1 = every rank but rank 0 sends its shard through pinned host memory, as between devices without peer access, even where a
  * direct copy would do (two contexts on one device included).
+ * "packet_tree_slots" (16 default, or 8; read when a scene is made on the context): child slots per node of the tree the cached
+ * packet walk uses: 16 = a tree of its own with thin nodes absorbed up to 16 children (fewer node steps; scenes whose tree of this
+ * kind would have 2^16 nodes or more keep 8), 8 = the wide tree the other walks use.
  * Results never depend on any of them (tests sweep them). */
 int mp_ctx_set_option(mp_ctx *ctx, const char *key, int value);
 /* Diagnostics.  "multi_staged_ranks": ranks of the last frame gathered on ctx (as ctxs[0] of mp_render_frame_multi /
@@ -314,7 +317,14 @@ int mp_scene_export(const mp_scene *scene, void *inner_nodes, void *packets, voi
  * the literal reference tree (InnerNode n = node n), walked by rays with an infinite inverse direction component.
  * nodes (nullable): count x 64 dwords = 8 child records {min.xyz, max.xyz (absolute f32), link, n}; link (u32 bits): inner =
  * node index << 6, leaf = first packet << 6 | real triangles (1..56), null = 0xFFFFFFF8; n (u32 bits, record 0 only) = index of
- * the last real child + 1.  absorbed = reference nodes that are no longer nodes of their own.  Any out pointer may be NULL. */
+ * the last real child + 1.  absorbed = reference nodes that are no longer nodes of their own.  Any out pointer may be NULL.
+ * which = 2: the tree of the cached packet walk as this scene has it.  Normally the PACKET tree -- the wide tree's absorption
+ * carried on to 16 slots per node: count x 128 dwords = 16 child records, unused slots are null links behind the last real child;
+ * where that walk keeps the wide tree (the scene was made on a context with "packet_tree_slots" = 8, or its packet tree would
+ * have 2^16 nodes or more, so: 16 records per node exactly when the option was 16 and count + 1 < 2^16) the wide tree as
+ * which = 0 gives it; a host-only scene has the default, 16.  In both cases 8 more dwords follow the nodes: the ROOT's record,
+ * which the wide and packet arrays keep behind their last node (an unbounded box and the root's link; the cached walk starts
+ * there), so nodes holds count x records per node x 8 + 8 dwords. */
 int mp_scene_device_tree(const mp_scene *scene, int which, float *nodes, uint32_t *count, uint32_t *root_link,
                          uint32_t *stack_bound, uint32_t *absorbed);
 

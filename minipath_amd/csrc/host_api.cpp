@@ -76,6 +76,7 @@ struct mp_ctx {
     uint32_t* d_counters = nullptr;
     std::atomic<uint32_t> next_counter{0};
     std::atomic<uint32_t> packet_stack_regs{64};
+    std::atomic<uint32_t> packet_tree_slots{16};  // slots per node of the cached packet walk's tree (read when a scene is uploaded)
     std::atomic<uint32_t> packet_samples{0};  // 0 = chosen by the launcher
     std::atomic<uint32_t> rays_per_lane{1};   // packet kernel: 1 = 64-ray walks, 2 = 128-ray walks (two rays per lane)
     std::atomic<uint32_t> blocks_per_cu{0};   // 0 = as many as fit (diagnostic knob: resident workgroups per CU)
@@ -189,6 +190,8 @@ struct mp_scene {
     void* d_vtex = nullptr;
     void* d_nodes_aos = nullptr;  // wide tree
     void* d_nodes_lit = nullptr;  // literal tree
+    void* d_nodes_pk = nullptr;   // packet tree (nullptr: the cached packet walk keeps the wide tree)
+    uint32_t packet_tree_slots = 16;  // the context's option when the scene was made (host-only scene: the default)
     uint32_t wide_nodes = 0, absorbed_nodes = 0;
     void* d_tris_aos = nullptr;
     void* d_pkt_valid = nullptr;
@@ -368,14 +371,20 @@ int upload_scene(mp_scene* s) {
     // infinite inverse direction component.  The sign-specialised slab test of the packet walk relies on min <= max for every
     // real child box of either.
     const std::vector<uint32_t> pkt_valid = packet_real_counts(h);
-    DeviceTree wide, lit;
+    DeviceTree wide, lit, pk;
+    bool use_pk = false;
     {
         std::string err;
         int trc = build_device_tree(h, pkt_valid, true, wide, err);
         if (!trc) trc = build_device_tree(h, pkt_valid, false, lit, err);
+        if (!trc && s->packet_tree_slots == 16u) {
+            trc = build_device_tree(h, pkt_valid, true, pk, err, 16);
+            use_pk = !trc && packet_tree_applies(pk, wide, lit, s->packet_tree_slots);
+        }
         if (trc) return fail(trc, err);
     }
-    s->dev.boxes_ordered = (wide.boxes_ordered && lit.boxes_ordered) ? 1u : 0u;
+    // (the packet tree holds the wide tree's boxes -- the same floats -- in other slots)
+    s->dev.boxes_ordered = (wide.boxes_ordered && lit.boxes_ordered && (!use_pk || pk.boxes_ordered)) ? 1u : 0u;
     s->wide_nodes = wide.count;
     s->absorbed_nodes = wide.absorbed;
     std::vector<float> tris_aos(np * 8 * kTriDwords + 4 * kTriDwords, 0.0f);  // + tail padding: the triangle loop prefetches up to two ahead
@@ -402,6 +411,7 @@ int upload_scene(mp_scene* s) {
     if ((rc = up(&s->d_vtex, h.vtex.data(), h.vtex.size() * 4))) return rc;
     if ((rc = up(&s->d_nodes_aos, wide.nodes.data(), wide.nodes.size() * 4))) return rc;
     if ((rc = up(&s->d_nodes_lit, lit.nodes.data(), lit.nodes.size() * 4))) return rc;
+    if (use_pk && (rc = up(&s->d_nodes_pk, pk.nodes.data(), pk.nodes.size() * 4))) return rc;
     if ((rc = up(&s->d_tris_aos, tris_aos.data(), tris_aos.size() * 4))) return rc;
     if ((rc = up(&s->d_pkt_valid, pkt_valid.data(), pkt_valid.size() * 4))) return rc;
     {
@@ -415,6 +425,7 @@ int upload_scene(mp_scene* s) {
     s->dev.sky = s->sky;
     MP_HIP(hipMemcpy(s->d_nodes_aos, wide.nodes.data(), wide.nodes.size() * 4, hipMemcpyHostToDevice));
     MP_HIP(hipMemcpy(s->d_nodes_lit, lit.nodes.data(), lit.nodes.size() * 4, hipMemcpyHostToDevice));
+    if (use_pk) MP_HIP(hipMemcpy(s->d_nodes_pk, pk.nodes.data(), pk.nodes.size() * 4, hipMemcpyHostToDevice));
     if (!tris_aos.empty()) MP_HIP(hipMemcpy(s->d_tris_aos, tris_aos.data(), tris_aos.size() * 4, hipMemcpyHostToDevice));
     if (!pkt_valid.empty()) MP_HIP(hipMemcpy(s->d_pkt_valid, pkt_valid.data(), pkt_valid.size() * 4, hipMemcpyHostToDevice));
     if (!shade.empty()) MP_HIP(hipMemcpy(s->d_shade, shade.data(), shade.size() * 4, hipMemcpyHostToDevice));
@@ -425,6 +436,10 @@ int upload_scene(mp_scene* s) {
     s->dev.vtex = static_cast<const float*>(s->d_vtex);
     s->dev.nodes_aos = static_cast<const float*>(s->d_nodes_aos);
     s->dev.nodes_lit = static_cast<const float*>(s->d_nodes_lit);
+    // the cached packet walk's tree: the packet tree, or the wide tree again (same pointer, 8-bit masks)
+    s->dev.nodes_pk = use_pk ? static_cast<const float*>(s->d_nodes_pk) : s->dev.nodes_aos;
+    s->dev.pk_count = use_pk ? pk.count : wide.count;
+    s->dev.pk_mask_bits = use_pk ? 16u : 8u;
     s->dev.tris_aos = static_cast<const float*>(s->d_tris_aos);
     s->dev.pkt_valid = static_cast<const uint32_t*>(s->d_pkt_valid);
     s->dev.root = wide.root;
@@ -454,6 +469,7 @@ int upload_scene(mp_scene* s) {
 
 int finish_scene(mp_ctx* ctx, std::unique_ptr<mp_scene> s, mp_scene** out) {
     s->ctx = ctx;
+    if (ctx) s->packet_tree_slots = ctx->packet_tree_slots.load();
     uint32_t mc = 0;
     for (uint32_t m : s->host.material) mc = std::max(mc, m);
     if (mc >= MP_MAX_MATERIALS) return fail(MP_ERR_INVALID, "material id out of range (MP_MAX_MATERIALS)");  // build_bvh / bvh_from_arrays reject these already
@@ -616,6 +632,11 @@ int mp_ctx_set_option(mp_ctx* ctx, const char* key, int value) {
     if (std::strcmp(key, "packet_stack_registers") == 0) {
         if (value < 1 || value > 64) return fail(MP_ERR_INVALID, "packet_stack_registers must be in 1..64");
         ctx->packet_stack_regs.store(static_cast<uint32_t>(value));
+        return MP_OK;
+    }
+    if (std::strcmp(key, "packet_tree_slots") == 0) {
+        if (value != 8 && value != 16) return fail(MP_ERR_INVALID, "packet_tree_slots must be 8 or 16");
+        ctx->packet_tree_slots.store(static_cast<uint32_t>(value));
         return MP_OK;
     }
     if (std::strcmp(key, "packet_mask_cache") == 0) {
@@ -987,7 +1008,7 @@ void scene_release(mp_scene* s) {
     }
     if (s->ctx) {
         DeviceGuard g(s->ctx->device);
-        for (void* p : {s->d_shade, s->d_vidx, s->d_vtex, s->d_nodes_aos, s->d_nodes_lit, s->d_tris_aos, s->d_pkt_valid})
+        for (void* p : {s->d_shade, s->d_vidx, s->d_vtex, s->d_nodes_aos, s->d_nodes_lit, s->d_nodes_pk, s->d_tris_aos, s->d_pkt_valid})
             if (p) (void)hipFree(p);
     }
     delete s;
@@ -1046,14 +1067,24 @@ int mp_scene_device_tree(const mp_scene* s, int which, float* nodes, uint32_t* c
                          uint32_t* absorbed) {
     return guarded([&]() -> int {
     if (!s) return fail(MP_ERR_INVALID, "scene is NULL");
-    if (which != 0 && which != 1) return fail(MP_ERR_INVALID, "which must be 0 (wide tree) or 1 (literal tree)");
+    if (which < 0 || which > 2) return fail(MP_ERR_INVALID, "which must be 0 (wide tree), 1 (literal tree) or 2 (packet tree)");
     if (s->dev.kind != 0u || (s->inst_of && !s->one_object)) return fail(MP_ERR_UNSUPPORTED, "only a TriangleBvh scene has a node tree of its own");
-    const HostBvh& h = s->inst_of ? s->inst_of->host : s->host;
+    const mp_scene* own = s->inst_of ? s->inst_of : s;
+    const HostBvh& h = own->host;
+    const std::vector<uint32_t> pkt_valid = packet_real_counts(h);
     DeviceTree t;
     std::string err;
-    const int rc = build_device_tree(h, packet_real_counts(h), which == 0, t, err);  // rebuilt from the host tree: same code, same floats as the upload
+    int rc = build_device_tree(h, pkt_valid, which != 1, t, err);  // rebuilt from the host tree: same code, same floats as the upload
+    if (!rc && which == 2 && own->packet_tree_slots == 16u) {  // the upload's choice between the packet tree and the wide tree
+        DeviceTree lit, pk;
+        rc = build_device_tree(h, pkt_valid, false, lit, err);
+        if (!rc) rc = build_device_tree(h, pkt_valid, true, pk, err, 16);
+        if (!rc && packet_tree_applies(pk, t, lit, own->packet_tree_slots)) t = std::move(pk);
+    }
     if (rc) return fail(rc, err);
-    if (nodes && t.count) std::memcpy(nodes, t.nodes.data(), static_cast<size_t>(t.count) * 64 * sizeof(float));
+    // which = 2: the ROOT's record behind the last node travels too (the cached walk starts there)
+    const size_t dwords = static_cast<size_t>(t.count) * t.slots * 8 + (which == 2 ? 8 : 0);
+    if (nodes && dwords) std::memcpy(nodes, t.nodes.data(), dwords * sizeof(float));
     if (count) *count = t.count;
     if (root_dlink) *root_dlink = t.root;
     if (stack_bound) *stack_bound = t.stack_bound;

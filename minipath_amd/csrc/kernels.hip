@@ -971,7 +971,7 @@ __device__ __forceinline__ void trace_packet_impl(const DevScene& sc, const Ray&
 }
 
 // Wave-uniform stack of the cached walk: three VGPRs used as 64-entry arrays.  An entry is a FRAME -- a visited node with the children
-// that are still to be popped (node << 8 | 8-bit mask) and the 64-bit mask of the rays that were live at the visit.  The frame on
+// that are still to be popped (node << MB | MB-bit mask, see trace_packet_cached) and the 64-bit mask of the rays that were live at the visit.  The frame on
 // top lives in scalar registers: popping a child is three scalar instructions, and the arrays are touched once per node visit
 // instead of once per child.
 struct RegStack3 {
@@ -1002,26 +1002,34 @@ struct RegStack3 {
 // child box may stick out of its parent's by an ulp).  No entry distance is stored or recomputed, no record is fetched at the
 // visit, and the child's record -- box and link -- is one 32-byte scalar load at the pop.  The root is child 0 of a pseudo-node
 // behind the last node: its record (device_tree.cpp) is an unbounded box, which every ray passes with t1 = 0 -- never culled (:28-32).
-template <int OCT>
+// The walk has a tree of its own, sc.nodes_pk: the PACKET tree (device_tree.cpp), MB = 16 child slots per node -- a masked-off child
+// costs nothing here, so wider nodes only save node steps -- or, for a scene whose packet tree would not fit the compact words,
+// the wide tree again with MB = 8 (DevScene::pk_mask_bits; the caller branches once per pass).  Frame words and cache entries are
+// node << MB | MB-bit child mask in one dword (fewer than 2^(32 - MB) nodes with the pseudo-node, checked at upload: an all-ones
+// tag is no node's); a node is MB records of 32 bytes.
+template <int OCT, int MB>
 __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ray& r, bool active, PacketHit& hit, uint32_t* mcache) {
-    kfp nodes = (kfp)(uintptr_t)sc.nodes_aos;
+    static_assert(MB == 8 || MB == 16, "8 slots (wide tree) or 16 (packet tree)");
+    constexpr uint32_t kSlotMask = (1u << MB) - 1u;
+    constexpr int kSlotShift = MB == 16 ? 4 : 3;  // a node is MB records
+    kfp nodes = (kfp)(uintptr_t)sc.nodes_pk;
     kfp tris = (kfp)(uintptr_t)sc.tris_aos;
     float best_t = FLT_MAX, bu = 0.0f, bv = 0.0f;  // best (:34-37)
     uint32_t bprim = kNoPrim;
     RegStack3 st;
     int sp = 0;                                   // frames below the current one
-    uint32_t cur = (sc.inner_count << 8) | 1u;    // current frame: node << 8 | children still to pop
+    uint32_t cur = (sc.pk_count << MB) | 1u;      // current frame: node << MB | children still to pop
     uint64_t pm = __ballot(active);               // ... and the rays that were live at its visit
     // (fetching the record of the child that is popped next ahead of its pop was built and measured slower: 27.0 against 24.3 ms)
     for (;;) {
-        if ((cur & 0xFFu) == 0u) {  // frame exhausted: back to the one below
+        if ((cur & kSlotMask) == 0u) {  // frame exhausted: back to the one below
             if (sp == 0) break;
             sp--;
             st.pop(sp, cur, pm);
         }
-        const uint32_t c = 31u - static_cast<uint32_t>(__builtin_clz(cur & 0xFFu));  // highest child first
+        const uint32_t c = 31u - static_cast<uint32_t>(__builtin_clz(cur & kSlotMask));  // highest child first
         cur &= ~(1u << c);
-        const uint32_t src = ((cur >> 8) << 3) | c;
+        const uint32_t src = ((cur >> MB) << kSlotShift) | c;
         const bool pon = __builtin_amdgcn_inverse_ballot_w64(pm);
         // (base + a 32-bit byte offset: s_load's register-offset form; fewer than 2^24 nodes, checked at upload)
         const krec8 rec = *reinterpret_cast<const __attribute__((address_space(4))) krec8*>(reinterpret_cast<const __attribute__((address_space(4))) char*>(nodes) + scalar_u(src * 32u));
@@ -1037,27 +1045,27 @@ __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ra
             const uint32_t cslot = static_cast<uint32_t>(kMaskCacheHeader) + (node & static_cast<uint32_t>(kMaskCacheEntries - 1));
             const uint32_t e = __builtin_amdgcn_readfirstlane(mcache[cslot]);
             uint32_t todo;
-            if (__builtin_expect((e >> 8) == node, 1)) {
-                todo = e & 0xFFu;
+            if (__builtin_expect((e >> MB) == node, 1)) {
+                todo = e & kSlotMask;
             } else {  // first visit of this node under the current bounds: lane j = child j, records through one vector load pair
                 MP_PROF_COUNT(0);
-                const int cj = static_cast<int>(threadIdx.x) & 7;
+                const int cj = static_cast<int>(threadIdx.x) & (MB - 1);
                 bool keep = false;
-                if ((threadIdx.x & 63u) < 8u) {
-                    const float4* rec4 = reinterpret_cast<const float4*>(sc.nodes_aos) + (static_cast<size_t>(node) * 8 + static_cast<size_t>(cj)) * 2;
+                if ((threadIdx.x & 63u) < static_cast<uint32_t>(MB)) {
+                    const float4* rec4 = reinterpret_cast<const float4*>(sc.nodes_pk) + (static_cast<size_t>(node) * MB + static_cast<size_t>(cj)) * 2;
                     const float4 c0 = rec4[0], c1 = rec4[1];  // {min.xyz, max.x} {max.yz, link, n}
                     const float bmn[3] = {c0.x, c0.y, c0.z}, bmx[3] = {c0.w, c1.x, c1.y};
                     keep = as_u(c1.z) != MP_LINK_NULL && bounds_may_hit<OCT>(reinterpret_cast<const float*>(mcache), bmn, bmx);
                 }
-                todo = static_cast<uint32_t>(__ballot(keep)) & 0xFFu;
-                if ((threadIdx.x & 63u) == 0u) mcache[cslot] = (node << 8) | todo;
+                todo = static_cast<uint32_t>(__ballot(keep)) & kSlotMask;
+                if ((threadIdx.x & 63u) == 0u) mcache[cslot] = (node << MB) | todo;
             }
             if (todo != 0u) {  // a new frame; the one it replaces goes to the arrays if it still has children
-                if ((cur & 0xFFu) != 0u) {
+                if ((cur & kSlotMask) != 0u) {
                     st.push(sp, cur, pm);
                     sp++;
                 }
-                cur = (node << 8) | todo;
+                cur = (node << MB) | todo;
                 pm = __ballot(lim >= 0.0f);
             }
         } else {
@@ -1167,15 +1175,27 @@ __device__ __forceinline__ void trace_packet(const DevScene& sc, const Ray& r, b
             const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
             if (MC) {  // kernels with a mask cache: the sign-specialised walks use it
                 mask_cache_begin_pass(mc, r, active, oct);
-                switch (oct) {
-                    case 0: trace_packet_cached<0>(sc, r, active, hit, mc.lds); return;
-                    case 1: trace_packet_cached<1>(sc, r, active, hit, mc.lds); return;
-                    case 2: trace_packet_cached<2>(sc, r, active, hit, mc.lds); return;
-                    case 3: trace_packet_cached<3>(sc, r, active, hit, mc.lds); return;
-                    case 4: trace_packet_cached<4>(sc, r, active, hit, mc.lds); return;
-                    case 5: trace_packet_cached<5>(sc, r, active, hit, mc.lds); return;
-                    case 6: trace_packet_cached<6>(sc, r, active, hit, mc.lds); return;
-                    default: trace_packet_cached<7>(sc, r, active, hit, mc.lds); return;
+                if (sc.pk_mask_bits == 16u) {  // the packet tree (wave-uniform: a kernel argument)
+                    switch (oct) {
+                        case 0: trace_packet_cached<0, 16>(sc, r, active, hit, mc.lds); return;
+                        case 1: trace_packet_cached<1, 16>(sc, r, active, hit, mc.lds); return;
+                        case 2: trace_packet_cached<2, 16>(sc, r, active, hit, mc.lds); return;
+                        case 3: trace_packet_cached<3, 16>(sc, r, active, hit, mc.lds); return;
+                        case 4: trace_packet_cached<4, 16>(sc, r, active, hit, mc.lds); return;
+                        case 5: trace_packet_cached<5, 16>(sc, r, active, hit, mc.lds); return;
+                        case 6: trace_packet_cached<6, 16>(sc, r, active, hit, mc.lds); return;
+                        default: trace_packet_cached<7, 16>(sc, r, active, hit, mc.lds); return;
+                    }
+                }
+                switch (oct) {  // the wide tree, 8-bit masks
+                    case 0: trace_packet_cached<0, 8>(sc, r, active, hit, mc.lds); return;
+                    case 1: trace_packet_cached<1, 8>(sc, r, active, hit, mc.lds); return;
+                    case 2: trace_packet_cached<2, 8>(sc, r, active, hit, mc.lds); return;
+                    case 3: trace_packet_cached<3, 8>(sc, r, active, hit, mc.lds); return;
+                    case 4: trace_packet_cached<4, 8>(sc, r, active, hit, mc.lds); return;
+                    case 5: trace_packet_cached<5, 8>(sc, r, active, hit, mc.lds); return;
+                    case 6: trace_packet_cached<6, 8>(sc, r, active, hit, mc.lds); return;
+                    default: trace_packet_cached<7, 8>(sc, r, active, hit, mc.lds); return;
                 }
             } else {
                 switch (oct) {

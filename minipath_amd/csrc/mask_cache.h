@@ -101,7 +101,7 @@ __device__ __forceinline__ void slab(float bnx, float bny, float bnz, float bxx,
 #ifndef MP_LEAF_ENTRIES
 #define MP_LEAF_ENTRIES 128
 #endif
-constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // direct-mapped: node index & 511 ; entry = node << 8 | mask
+constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // direct-mapped: node index & 511 ; entry = node << MB | MB-bit mask (the walk's MB: 16 / 8)
 constexpr int kMaskCacheHeader = 32;                        // B: [0..11] origin / inverse-direction bounds, [12] = sign pattern | 0x100 when valid (0xFFFFFFFF: none), [13..18] direction bounds
 constexpr int kLeafCacheEntries = MP_LEAF_ENTRIES;                      // direct-mapped: first packet of the leaf & 127 ; tag = first packet, mask = 64 bits (triangle i of the leaf)
 constexpr int kLeafTagBase = kMaskCacheHeader + kMaskCacheEntries;

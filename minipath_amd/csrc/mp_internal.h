@@ -60,26 +60,34 @@ int load_obj(const char* path, std::vector<float>& pos, std::vector<float>& nrm,
 // chain, depth and triangle count.
 int bvh_from_arrays(const mp_bvh_desc& d, HostBvh& out, std::string& err);
 
-// Traversal-format node array (device_tree.cpp): `count` nodes x 8 child records x 8 dwords (+ two records of tail padding; in the
-// wide tree the first of them is the ROOT's record: an unbounded box and the root's dlink, slot count * 8), the dlink of the
-// root, the exact traversal-stack bound and whether every real child box has min <= max.  wide = thin nodes absorbed into
-// their parents (the tree the walks use for rays with finite inverse directions); otherwise the literal reference tree.
+// Traversal-format node array (device_tree.cpp): `count` nodes x `slots` child records x 8 dwords (+ two records of tail padding;
+// in the wide and packet trees the first of them is the ROOT's record: an unbounded box and the root's dlink, slot
+// count * slots), the dlink of the root, the exact traversal-stack bound and whether every real child box has min <= max.
+// wide = thin nodes absorbed into their parents while a node keeps within `slots` (8: the WIDE tree, which the walks use for rays
+// with finite inverse directions; 16: the PACKET tree of the cached packet walk); otherwise the literal reference tree.
 struct DeviceTree {
     std::vector<float> nodes;
     uint32_t count = 0;
+    uint32_t slots = 8;
     uint32_t root = MP_LINK_NULL;
     uint32_t stack_bound = 1;
-    uint32_t absorbed = 0;       // reference nodes that no longer exist as nodes of their own (wide tree)
+    uint32_t frame_bound = 0;    // exact bound of the cached packet walk's frame stack (wide / packet tree)
+    uint32_t absorbed = 0;       // reference nodes that no longer exist as nodes of their own (wide / packet tree)
     bool boxes_ordered = true;
 };
 std::vector<uint32_t> packet_real_counts(const HostBvh& h);  // real (unpadded) triangles of each packet
-int build_device_tree(const HostBvh& h, const std::vector<uint32_t>& pkt_valid, bool wide, DeviceTree& out, std::string& err);
+int build_device_tree(const HostBvh& h, const std::vector<uint32_t>& pkt_valid, bool wide, DeviceTree& out, std::string& err,
+                      uint32_t slots = 8);
+// Whether the cached packet walk takes the 16-slot `packet` tree (compact words: node << 16 | 16-bit mask) or keeps the wide tree
+// (node << 8 | 8-bit mask): want_slots = the context's packet_tree_slots; fewer than 2^16 nodes with the root's pseudo-node.
+bool packet_tree_applies(const DeviceTree& packet, const DeviceTree& wide, const DeviceTree& lit, uint32_t want_slots);
 
 // ---- device scene ("traversal format") -------------------------------------------------------
 // nodes_aos : node_count x 8 children x 8 dwords {minx,miny,minz,maxx,maxy,maxz,dlink,n}: absolute decompressed child boxes;
 //             n (record 0 only) = index of the node's last real child + 1.  This is the WIDE tree (device_tree.cpp: thin nodes
 //             absorbed into their parents, bit-identical hits for rays with finite inverse directions); nodes_lit / root_lit are
-//             the literal reference tree in the same format, walked by rays with an infinite inverse direction component.
+//             the literal reference tree in the same format, walked by rays with an infinite inverse direction component;
+//             nodes_pk is the tree of the cached packet walk: the same format with 16 records per node (or nodes_aos again).
 // dlink     : device-private link (the reference's CompressedNodeLink idx<<3|count, mod.rs:57-114, re-encoded so that a leaf needs
 //             no side lookup): inner = node index << 6 ; leaf = first packet << 6 | real (unpadded) triangles of the leaf (1..56) ;
 //             null = MP_LINK_NULL unchanged (checked before decoding; scenes are limited to 2^24 nodes and 14.9 M packets:
@@ -129,6 +137,12 @@ struct DevScene {
     float sky = 1.0f;                  // ... and the sky radiance
     uint32_t inst_count = 0;           // build-defined object group: number of members; 0 = plain BVH
     const struct DevObject* objects = nullptr;  // ... and their descriptors (device)
+    // The tree of the cached packet walk (trace_packet_cached) and the format of its compact words (node << pk_mask_bits | child
+    // mask; a node is pk_mask_bits records of 32 bytes): the 16-slot packet tree (16), or -- a scene whose packet tree would have
+    // 2^16 nodes or more, or packet_tree_slots = 8 -- the wide tree itself (nodes_aos, inner_count; 8).
+    const float* nodes_pk = nullptr;
+    uint32_t pk_count = 0;
+    uint32_t pk_mask_bits = 8;
     uint32_t root = MP_LINK_NULL;    // dlink of the root (wide tree)
     uint32_t root_lit = MP_LINK_NULL;  // ... in the literal tree
     uint32_t inner_count = 0;        // nodes of the wide tree

@@ -17,6 +17,7 @@ class Context:
         _lib.check(_lib.lib().mp_ctx_create(int(device_id), C.byref(h)))
         self.handle = h
         self.device_id = int(device_id)
+        self.options = {}  # what set_option was given, by key
 
     @property
     def cu_count(self) -> int:
@@ -27,6 +28,7 @@ class Context:
     def set_option(self, key: str, value: int) -> None:
         """mp_ctx_set_option: tuning knobs (results never depend on them)."""
         _lib.check(_lib.lib().mp_ctx_set_option(self.handle, key.encode(), int(value)))
+        self.options[key] = int(value)
 
     def query(self, key: str) -> int:
         """mp_ctx_query: diagnostics ("multi_staged_ranks")."""
@@ -63,6 +65,8 @@ class TriangleBvh:
     def __init__(self, handle, ctx: Optional[Context]):
         self.handle = handle
         self.ctx = ctx
+        # the context's "packet_tree_slots" now, when the scene is made (a host-only scene has the default): device_tree(packet=True)
+        self.packet_tree_slots = ctx.options.get("packet_tree_slots", 16) if ctx is not None else 16
 
     @classmethod
     def with_obj(cls, path: str, ctx: Optional[Context] = None) -> "TriangleBvh":
@@ -141,15 +145,22 @@ class TriangleBvh:
         i = self.info()
         return np.array(list(i.bbox_min), np.float32), np.array(list(i.bbox_max), np.float32)
 
-    def device_tree(self, literal: bool = False):
+    def device_tree(self, literal: bool = False, packet: bool = False):
         """The traversal-format node array the kernels walk (mp_scene_device_tree; diagnostics / tests): returns
-        (nodes (n, 8, 8) u32 view of {min.xyz, max.xyz, link, n} records, root link, stack bound, absorbed reference nodes).
-        literal=False: the wide tree (thin nodes absorbed into their parents); True: the literal reference tree."""
+        (nodes (n, slots, 8) u32 view of {min.xyz, max.xyz, link, n} records, root link, stack bound, absorbed reference nodes).
+        literal=False: the wide tree (thin nodes absorbed into their parents); True: the literal reference tree; 8 slots both.
+        packet=True: the tree of the cached packet walk as this scene has it -- 16 slots per node, or the wide tree where the walk
+        keeps it (Context option "packet_tree_slots" = 8 when the scene was made, or a packet tree of 2^16 nodes or more) -- and a
+        fifth value, the root's record (u32[8]) that follows the last node."""
         n, root, bound, absorbed = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
-        which = 1 if literal else 0
+        which = 2 if packet else 1 if literal else 0
         _lib.check(_lib.lib().mp_scene_device_tree(self.handle, which, None, C.byref(n), C.byref(root), C.byref(bound), C.byref(absorbed)))
-        nodes = np.zeros((n.value, 8, 8), np.uint32)
-        _lib.check(_lib.lib().mp_scene_device_tree(self.handle, which, nodes.ctypes.data, None, None, None, None))
+        slots = 16 if packet and getattr(self, "packet_tree_slots", 16) == 16 and n.value + 1 < (1 << 16) else 8
+        flat = np.zeros(n.value * slots * 8 + (8 if packet else 0), np.uint32)
+        _lib.check(_lib.lib().mp_scene_device_tree(self.handle, which, flat.ctypes.data, None, None, None, None))
+        nodes = flat[:n.value * slots * 8].reshape(n.value, slots, 8)
+        if packet:
+            return nodes, root.value, bound.value, absorbed.value, flat[n.value * slots * 8:].copy()
         return nodes, root.value, bound.value, absorbed.value
 
     def export(self, with_material: bool = False):
