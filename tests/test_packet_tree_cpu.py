@@ -17,19 +17,24 @@ import pytest
 
 import minipath_amd as mp
 from minipath_amd import _lib, scenes
-from tests import meshes
+from tests import graft_model, meshes
 from tests.conftest import TEAPOT
 
 NULL = 0xFFFFFFF8
 F = np.float32
 # the stand-in at a small detail (thin binary top, non-nestable nodes: asserted below), the teapot, two meshes (`doubled`: exact ties)
 SCENES = ["teapot", "atrium:0.1", "soup_5000", "grid_40+doubled"]
+# ... and the teapot behind a filler of childless nodes (tests/graft_model.py), as many as the 16-bit format just holds: 65 534 nodes
+# of the packet tree, the teapot's leaves in the last of them
+GRAFT = "graft"
 
 
 @functools.lru_cache(maxsize=None)
 def _host(name):
     if name == "teapot":
         return mp.TriangleBvh.with_obj(TEAPOT)
+    if name == GRAFT:
+        return graft_model.grafted_host(graft_model.top_filler_size())
     if name.startswith("atrium"):
         return mp.TriangleBvh.build(*scenes.atrium(1, float(name.split(":")[1])))
     base, _, mod = name.partition("+")
@@ -69,13 +74,22 @@ def _leaf_order(nodes, root):
 
 
 def _subtree_signatures(nodes, root):
-    """{node index: (first leaf link in ascending-child order, number of leaves)}"""
+    """{node index: (first terminal in ascending-child order, number of terminals)}.  A terminal is a leaf, named by its link, or a
+    node without children (the filler of the grafted scene), named by its place among such nodes in a depth-first walk in
+    ascending-child order: absorption keeps that order, so the name is the same on every tree."""
     first, count, order, stack = {}, {}, [], [root >> 6]
     while stack:
         n = stack.pop()
         order.append(n)
-        stack.extend(l >> 6 for _, l in _slots(nodes, n) if (l & 63) == 0)
+        stack.extend(l >> 6 for _, l in reversed(_slots(nodes, n)) if (l & 63) == 0)
+    empties = 0
+    for n in order:  # pre-order, children ascending
+        if not _slots(nodes, n):
+            first[n], count[n] = ("childless", empties), 1
+            empties += 1
     for n in reversed(order):
+        if n in first:
+            continue
         f, c = None, 0
         for _, l in _slots(nodes, n):
             lf, lc = (l, 1) if l & 63 else (first[l >> 6], count[l >> 6])
@@ -85,7 +99,7 @@ def _subtree_signatures(nodes, root):
     return first, count
 
 
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + [GRAFT])
 def test_packet_tree_structure_and_containment(name):
     host, t = _host(name), _trees(name)
     pk, proot, pbound, absorbed, _ = t["packet"]
@@ -99,7 +113,12 @@ def test_packet_tree_structure_and_containment(name):
     real = pk[:, :, 6] != NULL
     # at most 16 real children (the shape), at least two, null links only behind the last real child, n = their number
     assert np.all(real[:, :-1] >= real[:, 1:])
-    assert np.all(real.sum(1) >= 2) and np.array_equal(pk[:, 0, 7], real.sum(1))
+    assert np.array_equal(pk[:, 0, 7], real.sum(1))
+    if name == GRAFT:  # the nodes at the bottom of the filler's heap have no children at all and are never absorbed: the literal tree's
+        assert np.all((real.sum(1) >= 2) | (real.sum(1) == 0))
+        assert (real.sum(1) == 0).sum() == ((lit[:, :, 6] != NULL).sum(1) == 0).sum() > pk.shape[0] // 2
+    else:
+        assert np.all(real.sum(1) >= 2)
     # unused slots are zero boxes
     assert not pk[:, :, :6][~real].any()
     # children have larger indices than their parent, every node but the root has exactly one parent: pre-order numbering
@@ -145,7 +164,7 @@ def test_packet_tree_structure_and_containment(name):
     assert pbound >= 1
 
 
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + [GRAFT])
 def test_root_pseudo_record(name):
     """The record behind the last node (record count * slots) is the root's: an unbounded box, which every ray passes with t1 = 0,
     and the root's link.  The cached walk starts there: child 0 of pseudo-node `count`, which the 16-bit format must hold."""
@@ -155,7 +174,7 @@ def test_root_pseudo_record(name):
     assert int(rec[6]) == proot == 0  # node 0 << 6
 
 
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + [GRAFT])
 def test_other_exports_do_not_move(name):
     """which = 0 / 1 after the packet export: the arrays of before.  (The fallback -- "packet_tree_slots" = 8: the export is the wide
     tree byte for byte -- needs a context to set the option on: tests/test_gpu_packet_tree.py.)"""
@@ -167,8 +186,9 @@ def test_other_exports_do_not_move(name):
         _lib.check(_lib.lib().mp_scene_device_tree(host.handle, 3, None, C.byref(n), None, None, None))
 
 
-def _walk(nodes, root, tris_of, o, d, inv):
-    """the reference's walk (ray_bvh_intersection.rs:26-62) on a device-format tree: (leaf sequence, best t, deepest stack)"""
+def _walk(nodes, root, tris_of, o, d, inv, childless=None):
+    """the reference's walk (ray_bvh_intersection.rs:26-62) on a device-format tree: (leaf sequence, best t, deepest stack);
+    childless: a list that receives the visited nodes without children"""
     best = np.finfo(F).max
     stack = [(root, F(-np.inf))]
     seq, deepest = [], 1
@@ -183,6 +203,10 @@ def _walk(nodes, root, tris_of, o, d, inv):
                 best = t
             continue
         sl = _slots(nodes, link >> 6)
+        if not sl:  # a node without children (the grafted scene's filler): visited, nothing pushed
+            if childless is not None:
+                childless.append(link >> 6)
+            continue
         boxes = np.array([b for b, _ in sl], F)
         a = (boxes[:, :3] - o) * inv
         c = (boxes[:, 3:] - o) * inv
@@ -196,7 +220,7 @@ def _walk(nodes, root, tris_of, o, d, inv):
     return seq, best, deepest
 
 
-@pytest.mark.parametrize("name", SCENES)
+@pytest.mark.parametrize("name", SCENES + [GRAFT])
 def test_walk_reaches_the_same_leaves_on_all_three_trees(name):
     host, t = _host(name), _trees(name)
     lit, lroot, lbound, _ = t["lit"]
@@ -238,6 +262,12 @@ def test_walk_reaches_the_same_leaves_on_all_three_trees(name):
     d /= np.linalg.norm(d, axis=1, keepdims=True)
     planes = lit[:, :, :6].view(F).reshape(-1, 6)
     planes = planes[np.isfinite(planes).all(1) & (lit[:, :, 6].reshape(-1) != NULL)]
+    if name == GRAFT:
+        # the rays of this part are aimed at the teapot's boxes; a box that touches the filler's corner box (the root's slot 0) would
+        # send its rays through all 66 k filler nodes: those are the bundle's below
+        corner = lit[0, 0, :6].view(F)
+        planes = planes[~(planes[:, :3] <= corner[3:]).all(1)]
+        assert planes.shape[0] > 100
     for k in range(0, 80):
         b = planes[rng.integers(0, planes.shape[0])]
         if k < 40:
@@ -271,3 +301,27 @@ def test_walk_reaches_the_same_leaves_on_all_three_trees(name):
             assert deep <= bound
         visited += len(ls)
     assert visited > 50  # the rays do reach leaves
+    if name != GRAFT:
+        return
+    # a bundle into the filler's corner box, from outside the scene and from inside it: every tree visits the same nodes without
+    # children -- none of them is ever absorbed --, in the same order up to their numbering, and then the teapot's leaves as the others do
+    n_filler = graft_model.top_filler_size()
+    tgt = (corner[:3].astype(np.float64) + corner[3:].astype(np.float64)) / 2
+    for toward in (np.array([0.66, 0.45, 0.6]), np.array([-0.5, -0.62, -0.6])):
+        ob = (tgt - toward * (0.3 if toward[0] > 0 else -0.1) * float(ext.max())).astype(F)
+        db = (tgt - ob.astype(np.float64)).astype(F)
+        db /= np.linalg.norm(db)
+        ib = (F(1) / db).astype(F)
+        assert np.isfinite(ib).all()
+        seen = {}
+        for kind in ("lit", "wide", "packet"):
+            nodes, root, bound = t[kind][:3]
+            seen[kind] = []
+            s, bt, deep = _walk(nodes, root, tris_of, ob, db, ib, seen[kind])
+            assert deep <= bound
+            if kind == "lit":
+                ls, lt = s, bt
+            assert s == ls and np.array_equal(np.array([bt], F).view(np.uint32), np.array([lt], F).view(np.uint32)), kind
+        counts = {k: len(v) for k, v in seen.items()}
+        assert counts["lit"] == counts["wide"] == counts["packet"] > n_filler // 2, counts
+        assert len(set(seen["packet"])) == counts["packet"] and max(seen["packet"]) > (1 << 15)
