@@ -25,7 +25,7 @@
 #ifdef MP_PROF_MISSES  // profiling builds only (tools/build_variant.sh): slow-path calls of the mask cache, read by mp_prof_read
 namespace mp {
 namespace {
-__device__ unsigned long long g_prof[4];
+__device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask builds [2] inner links followed [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk
 }  // namespace
 }  // namespace mp
 #define MP_PROF_COUNT(i) do { if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_prof[i], 1ull); } while (0)
@@ -1002,34 +1002,45 @@ struct RegStack3 {
 // child box may stick out of its parent's by an ulp).  No entry distance is stored or recomputed, no record is fetched at the
 // visit, and the child's record -- box and link -- is one 32-byte scalar load at the pop.  The root is child 0 of a pseudo-node
 // behind the last node: its record (device_tree.cpp) is an unbounded box, which every ray passes with t1 = 0 -- never culled (:28-32).
-// The walk has a tree of its own, sc.nodes_pk: the PACKET tree (device_tree.cpp), MB = 16 child slots per node -- a masked-off child
-// costs nothing here, so wider nodes only save node steps -- or, for a scene whose packet tree would not fit the compact words,
-// the wide tree again with MB = 8 (DevScene::pk_mask_bits; the caller branches once per pass).  Frame words and cache entries are
-// node << MB | MB-bit child mask in one dword (fewer than 2^(32 - MB) nodes with the pseudo-node, checked at upload: an all-ones
-// tag is no node's); a node is MB records of 32 bytes.
-template <int OCT, int MB>
-__device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ray& r, bool active, PacketHit& hit, uint32_t* mcache) {
-    static_assert(MB == 8 || MB == 16, "8 slots (wide tree) or 16 (packet tree)");
-    constexpr uint32_t kSlotMask = (1u << MB) - 1u;
-    constexpr int kSlotShift = MB == 16 ? 4 : 3;  // a node is MB records
+// The walk has a tree of its own, sc.nodes_pk: the PACKET tree (device_tree.cpp), 16 child slots per node, or, for a scene whose
+// packet tree would not fit 16-bit node indices, the wide tree again with 8 (DevScene::pk_mask_bits = slots per node, a runtime
+// value here: only the list builder needs it).
+// A frame is a LIST (mask_cache.h, unit_list_build): the kept children of the node, with the kept children of absorbed inner
+// children in their place.  Frame word = (dword index of the list's first entry in the wave's cache) << 16 | entries still to pop;
+// popping takes the last entry -- the record index node * slots + slot -- from LDS.  An inner link is looked up by node index in
+// the unit's table; a miss builds the list (unit_list_slow, a real call: once or twice per unit).  Returns false when a list did
+// not fit the arena while frames of this walk still pointed into it: table and arena are reset, and the caller walks this pass
+// without the cache (the same hits: every walk computes the reference's).  (Beginning the pass again as a cached walk on the
+// emptied arena was built and measured: the restart state costs the flagship 0.6 ms, 15.3 against 14.7 ms, for a case that its
+// frame never meets -- tools/cache_miss_count.py prints how often a frame does.)
+template <int OCT>
+__device__ __noinline__ uint32_t unit_list_slow(const float* __restrict__ nodes_pk, uint32_t* mcache, uint32_t node, uint32_t slots) {
+    return unit_list_build(reinterpret_cast<const float4*>(nodes_pk), mcache, node, slots,
+                           [](const float* b, const float bmn[3], const float bmx[3]) { return bounds_may_hit<OCT>(b, bmn, bmx); });
+}
+template <int OCT>
+__device__ __forceinline__ bool trace_packet_cached(const DevScene& sc, const Ray& r, bool active, PacketHit& hit, uint32_t* mcache) {
+    static_assert(kNullLink == MP_LINK_NULL, "mask_cache.h's copy of the null link");
     kfp nodes = (kfp)(uintptr_t)sc.nodes_pk;
     kfp tris = (kfp)(uintptr_t)sc.tris_aos;
     float best_t = FLT_MAX, bu = 0.0f, bv = 0.0f;  // best (:34-37)
     uint32_t bprim = kNoPrim;
     RegStack3 st;
     int sp = 0;                                   // frames below the current one
-    uint32_t cur = (sc.pk_count << MB) | 1u;      // current frame: node << MB | children still to pop
-    uint64_t pm = __ballot(active);               // ... and the rays that were live at its visit
+    // the first frame: a list of one entry, the root's record (child 0 of the pseudo-node behind the last node); every lane stores the same dword
+    mcache[kRootListSlot] = sc.pk_count * sc.pk_mask_bits;
+    wave_lds_sync();
+    uint32_t cur = (static_cast<uint32_t>(kRootListSlot) << 16) | 1u;
+    uint64_t pm = __ballot(active);               // the rays that were live at the current frame's visit
     // (fetching the record of the child that is popped next ahead of its pop was built and measured slower: 27.0 against 24.3 ms)
     for (;;) {
-        if ((cur & kSlotMask) == 0u) {  // frame exhausted: back to the one below
+        if ((cur & 0xFFFFu) == 0u) {  // frame exhausted: back to the one below
             if (sp == 0) break;
             sp--;
             st.pop(sp, cur, pm);
         }
-        const uint32_t c = 31u - static_cast<uint32_t>(__builtin_clz(cur & kSlotMask));  // highest child first
-        cur &= ~(1u << c);
-        const uint32_t src = ((cur >> MB) << kSlotShift) | c;
+        cur -= 1u;  // last entry first
+        const uint32_t src = __builtin_amdgcn_readfirstlane(mcache[(cur >> 16) + (cur & 0xFFFFu)]);
         const bool pon = __builtin_amdgcn_inverse_ballot_w64(pm);
         // (base + a 32-bit byte offset: s_load's register-offset form; fewer than 2^24 nodes, checked at upload)
         const krec8 rec = *reinterpret_cast<const __attribute__((address_space(4))) krec8*>(reinterpret_cast<const __attribute__((address_space(4))) char*>(nodes) + scalar_u(src * 32u));
@@ -1042,30 +1053,27 @@ __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ra
         if ((link & 63u) == 0u) {  // inner node (device link, mp_internal.h)
             MP_PROF_COUNT(2);
             const uint32_t node = link >> 6;
-            const uint32_t cslot = static_cast<uint32_t>(kMaskCacheHeader) + (node & static_cast<uint32_t>(kMaskCacheEntries - 1));
-            const uint32_t e = __builtin_amdgcn_readfirstlane(mcache[cslot]);
-            uint32_t todo;
-            if (__builtin_expect((e >> MB) == node, 1)) {
-                todo = e & kSlotMask;
-            } else {  // first visit of this node under the current bounds: lane j = child j, records through one vector load pair
+            const uint32_t slot = node_slot(node);
+            const uint32_t tag = __builtin_amdgcn_readfirstlane(mcache[static_cast<uint32_t>(kMaskCacheHeader) + slot]);
+            uint32_t list = __builtin_amdgcn_readfirstlane(mcache[static_cast<uint32_t>(kNodeListBase) + slot]);
+            if (__builtin_expect(tag != node, 0)) {  // first visit of this node under the current bounds, or its entry was evicted
                 MP_PROF_COUNT(0);
-                const int cj = static_cast<int>(threadIdx.x) & (MB - 1);
-                bool keep = false;
-                if ((threadIdx.x & 63u) < static_cast<uint32_t>(MB)) {
-                    const float4* rec4 = reinterpret_cast<const float4*>(sc.nodes_pk) + (static_cast<size_t>(node) * MB + static_cast<size_t>(cj)) * 2;
-                    const float4 c0 = rec4[0], c1 = rec4[1];  // {min.xyz, max.x} {max.yz, link, n}
-                    const float bmn[3] = {c0.x, c0.y, c0.z}, bmx[3] = {c0.w, c1.x, c1.y};
-                    keep = as_u(c1.z) != MP_LINK_NULL && bounds_may_hit<OCT>(reinterpret_cast<const float*>(mcache), bmn, bmx);
+                if (tag != 0xFFFFFFFFu) MP_PROF_COUNT(4);
+                list = __builtin_amdgcn_readfirstlane(unit_list_slow<OCT>(sc.nodes_pk, mcache, node, sc.pk_mask_bits));
+                if (list == kListOverflow) {
+                    if (sp != 0 || (cur & 0xFFFFu) != 0u) {  // frames of this walk point into the arena that was reset
+                        MP_PROF_COUNT(6);
+                        return false;
+                    }
+                    list = __builtin_amdgcn_readfirstlane(unit_list_slow<OCT>(sc.nodes_pk, mcache, node, sc.pk_mask_bits));  // fits the empty arena
                 }
-                todo = static_cast<uint32_t>(__ballot(keep)) & kSlotMask;
-                if ((threadIdx.x & 63u) == 0u) mcache[cslot] = (node << MB) | todo;
             }
-            if (todo != 0u) {  // a new frame; the one it replaces goes to the arrays if it still has children
-                if ((cur & kSlotMask) != 0u) {
+            if ((list & 0xFFFFu) != 0u) {  // a new frame; the one it replaces goes to the arrays if it still has entries
+                if ((cur & 0xFFFFu) != 0u) {
                     st.push(sp, cur, pm);
                     sp++;
                 }
-                cur = (node << MB) | todo;
+                cur = list;
                 pm = __ballot(lim >= 0.0f);
             }
         } else {
@@ -1144,6 +1152,7 @@ __device__ __forceinline__ void trace_packet_cached(const DevScene& sc, const Ra
         }
     }
     hit.t = best_t; hit.u = bu; hit.v = bv; hit.prim = bprim;
+    return true;
 }
 
 // OCTANTS: also instantiate the eight sign-specialised walks (the production kernels; the rest keep the generic slab).
@@ -1175,28 +1184,18 @@ __device__ __forceinline__ void trace_packet(const DevScene& sc, const Ray& r, b
             const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
             if (MC) {  // kernels with a mask cache: the sign-specialised walks use it
                 mask_cache_begin_pass(mc, r, active, oct);
-                if (sc.pk_mask_bits == 16u) {  // the packet tree (wave-uniform: a kernel argument)
-                    switch (oct) {
-                        case 0: trace_packet_cached<0, 16>(sc, r, active, hit, mc.lds); return;
-                        case 1: trace_packet_cached<1, 16>(sc, r, active, hit, mc.lds); return;
-                        case 2: trace_packet_cached<2, 16>(sc, r, active, hit, mc.lds); return;
-                        case 3: trace_packet_cached<3, 16>(sc, r, active, hit, mc.lds); return;
-                        case 4: trace_packet_cached<4, 16>(sc, r, active, hit, mc.lds); return;
-                        case 5: trace_packet_cached<5, 16>(sc, r, active, hit, mc.lds); return;
-                        case 6: trace_packet_cached<6, 16>(sc, r, active, hit, mc.lds); return;
-                        default: trace_packet_cached<7, 16>(sc, r, active, hit, mc.lds); return;
-                    }
+                bool done;
+                switch (oct) {
+                    case 0: done = trace_packet_cached<0>(sc, r, active, hit, mc.lds); break;
+                    case 1: done = trace_packet_cached<1>(sc, r, active, hit, mc.lds); break;
+                    case 2: done = trace_packet_cached<2>(sc, r, active, hit, mc.lds); break;
+                    case 3: done = trace_packet_cached<3>(sc, r, active, hit, mc.lds); break;
+                    case 4: done = trace_packet_cached<4>(sc, r, active, hit, mc.lds); break;
+                    case 5: done = trace_packet_cached<5>(sc, r, active, hit, mc.lds); break;
+                    case 6: done = trace_packet_cached<6>(sc, r, active, hit, mc.lds); break;
+                    default: done = trace_packet_cached<7>(sc, r, active, hit, mc.lds); break;
                 }
-                switch (oct) {  // the wide tree, 8-bit masks
-                    case 0: trace_packet_cached<0, 8>(sc, r, active, hit, mc.lds); return;
-                    case 1: trace_packet_cached<1, 8>(sc, r, active, hit, mc.lds); return;
-                    case 2: trace_packet_cached<2, 8>(sc, r, active, hit, mc.lds); return;
-                    case 3: trace_packet_cached<3, 8>(sc, r, active, hit, mc.lds); return;
-                    case 4: trace_packet_cached<4, 8>(sc, r, active, hit, mc.lds); return;
-                    case 5: trace_packet_cached<5, 8>(sc, r, active, hit, mc.lds); return;
-                    case 6: trace_packet_cached<6, 8>(sc, r, active, hit, mc.lds); return;
-                    default: trace_packet_cached<7, 8>(sc, r, active, hit, mc.lds); return;
-                }
+                if (done) return;  // (else: a list did not fit the arena in mid-walk -- the generic walk below, from the start)
             } else {
                 switch (oct) {
                     case 0: trace_packet_impl<1, 0>(sc, r, active, st, hit); return;
@@ -3119,9 +3118,15 @@ int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixe
 }  // namespace mp
 
 #ifdef MP_PROF_MISSES
-extern "C" int mp_prof_read(unsigned long long* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mp::g_prof), sizeof(unsigned long long) * 4) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[4] = {0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mp::g_prof), z, sizeof(z)) != hipSuccess) return 1; }
+extern "C" int mp_prof_read8(unsigned long long* out, int reset) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mp::g_prof), sizeof(unsigned long long) * 8) != hipSuccess) return 1;
+    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mp::g_prof), z, sizeof(z)) != hipSuccess) return 1; }
+    return 0;
+}
+extern "C" int mp_prof_read(unsigned long long* out, int reset) {  // the first four
+    unsigned long long all[8];
+    if (mp_prof_read8(all, reset) != 0) return 1;
+    for (int i = 0; i < 4; i++) out[i] = all[i];
     return 0;
 }
 #endif

@@ -2,7 +2,7 @@
 // prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
 // that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
 // per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define
-// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES before including it.
+// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES / MP_ARENA_ENTRIES / MP_NODE_SLOT_MASK before including it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,9 +74,9 @@ __device__ __forceinline__ void slab(float bnx, float bny, float bnz, float bxx,
 // the packet -- componentwise min / max of the origins and inverse directions -- proves it.  Evaluating that test per node visit
 // (lane j = child j, the records through a vector load) was built first and ran slower than it saved (profiles/r03_notes.md).
 // What pays is doing it ONCE PER WORK UNIT: a unit shoots 8-16 passes through the same 2-4 pixels, and one set of bounds B that
-// contains every pass's rays gives one 8-bit "children that may be hit" mask per node, cached in LDS (the packet kernel uses no
-// other LDS).  Every pass checks, lane by lane, that its ray lies inside B (no reduction), and while that holds and the sign
-// pattern is the same, a node visit costs one LDS lookup and the exact per-ray slab tests of the surviving children only.  B starts
+// contains every pass's rays gives one "children that may be hit" mask per node, from which the unit's child lists are built once and
+// cached in LDS (unit_list_build below; the packet kernel uses no other LDS).  Every pass checks, lane by lane, that its ray lies inside B (no reduction), and while that holds and the sign
+// pattern is the same, opening a node costs one LDS lookup and the exact per-ray slab tests of the surviving children only.  B starts
 // as the bounds of the unit's corner rays, computed from the camera (mask_cache_begin_unit), or, where that declines, as the bounds
 // of the first pass (wave reductions) widened by MP_MCACHE_PAD of their extent; a pass that does not fit widens B and clears the
 // cache.
@@ -93,20 +93,46 @@ __device__ __forceinline__ void slab(float bnx, float bny, float bnz, float bxx,
 #ifndef MP_MCACHE_PAD
 #define MP_MCACHE_PAD 0.25f  // widening of the unit's bounds on either side, in extents of the pass that sets them (A/B: 0.0625 .. 1, profiles/r03_notes.md)
 #endif
-// Table sizes (powers of two).  Counted on the metric's frame (tools/cache_miss_count.py, 16 passes per unit): 17.4 node-mask and 6.1
-// leaf-mask slow paths per unit, 1.08 bounds (re)sets; 256 / 256 entries: 22.8 and 5.1 (20.05 against 20.14 ms), 256 / 128: 20.23 ms.
+// Table sizes.  The node table (per-unit child LISTS: see unit_list_build below) is a direct-mapped table of MP_NODE_ENTRIES tags
+// (node index; slot = node_slot(node)) with one value dword each (list offset << 16 | entries) and an arena of MP_ARENA_ROOM list
+// entries; together they take the 512 dwords the node masks had, so that the wave's LDS stays at 928 dwords (launch_plan.h).
+// How the split follows from the counts (tools/unit_list_count.py, tests/test_unit_lists_cpu.py): a unit of the metric's frame builds
+// 1.20 lists (1.55 on the wide tree), the longest 29 entries; units of the small eviction frame, whose pixels cover more of the
+// scene, 1.4 lists, the longest 129 entries, and 34 evictions in 512 units at 64 slots on the wide tree.  So the table is small --
+// 64 slots are forty times the lists of a unit, and fewer would only add evictions -- and everything else goes to the arena: 384
+// entries are three times the longest list counted, so that a unit's lists fit without a reset.  The leaf table is as before
+// (tools/cache_miss_count.py: 5.8 leaf-mask slow paths per unit at 128 entries).
 #ifndef MP_NODE_ENTRIES
-#define MP_NODE_ENTRIES 512
+#define MP_NODE_ENTRIES 64
 #endif
 #ifndef MP_LEAF_ENTRIES
 #define MP_LEAF_ENTRIES 128
 #endif
-constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // direct-mapped: node index & 511 ; entry = node << MB | MB-bit mask (the walk's MB: 16 / 8)
+#ifndef MP_ARENA_ENTRIES
+#define MP_ARENA_ENTRIES 384  // list entries a unit may hold (test builds: fewer, the LDS layout stays)
+#endif
+#ifndef MP_ARENA_ROOM
+#define MP_ARENA_ROOM 384  // dwords of the arena in the layout
+#endif
+#ifndef MP_NODE_SLOT_MASK
+#define MP_NODE_SLOT_MASK 0xFFFFFFFFu  // test builds: 3 makes a table of four slots (all-ones: the AND folds away)
+#endif
+constexpr int kMaskCacheEntries = MP_NODE_ENTRIES;                      // node tags: slot node_slot(node) holds the node's index; the LAST tag dword holds ~(arena entries in use)
 constexpr int kMaskCacheHeader = 32;                        // B: [0..11] origin / inverse-direction bounds, [12] = sign pattern | 0x100 when valid (0xFFFFFFFF: none), [13..18] direction bounds
 constexpr int kLeafCacheEntries = MP_LEAF_ENTRIES;                      // direct-mapped: first packet of the leaf & 127 ; tag = first packet, mask = 64 bits (triangle i of the leaf)
 constexpr int kLeafTagBase = kMaskCacheHeader + kMaskCacheEntries;
 constexpr int kLeafMaskBase = kLeafTagBase + kLeafCacheEntries;   // uint2 per entry (8-byte aligned)
-constexpr int kMaskCacheDwords = kLeafMaskBase + 2 * kLeafCacheEntries;
+// [kMaskCacheHeader, kLeafMaskBase) is what the clears of mask_cache_begin_pass / mask_cache_begin_unit set to all-ones: no node and
+// no leaf has that tag, and the arena is empty (~0xFFFFFFFF = 0 entries in use).  Behind the leaf masks, untouched by the clears:
+constexpr int kNodeListBase = kLeafMaskBase + 2 * kLeafCacheEntries;  // value of node slot i: (first entry's dword index in the wave's cache) << 16 | entries ; the LAST value dword holds the root's record index (the walk's first frame)
+constexpr int kArenaBase = kNodeListBase + kMaskCacheEntries;         // list entries: record indices node * slots + slot into the walked tree
+constexpr int kArenaRoom = MP_ARENA_ROOM;
+constexpr int kArenaEntries = MP_ARENA_ENTRIES;
+constexpr int kMaskCacheDwords = kArenaBase + kArenaRoom;
+constexpr int kArenaTopSlot = kMaskCacheHeader + kMaskCacheEntries - 1;
+constexpr int kRootListSlot = kNodeListBase + kMaskCacheEntries - 1;
+static_assert((kMaskCacheEntries & (kMaskCacheEntries - 1)) == 0 && kMaskCacheEntries >= 4, "the node table's slot mask");
+static_assert(kArenaEntries >= 16 && kArenaEntries <= kArenaRoom, "an unexpanded list (at most 16 entries) fits the empty arena");
 static_assert((kLeafMaskBase % 2) == 0 && (kMaskCacheDwords % 4) == 0, "LDS alignment of the leaf masks / of the next wave's header");
 constexpr float kCoordCap = 1073741824.0f;                  // 2^30: magnitude bound of ray origins and triangle vertices for the triangle masks (see tri_may_hit)
 struct MaskCache {
@@ -308,6 +334,128 @@ __device__ __forceinline__ bool bounds_may_hit(const float* b, const float bmn[3
     }
     const float t1 = fmaxf(fmaxf(L[0], 0.0f), fmaxf(L[1], L[2])), t2 = fminf(U[0], fminf(U[1], U[2]));
     return !(t1 > t2);
+}
+
+// ---- per-unit child LISTS: the kept children of a node, with kept descendants in place of the children that need no test --------
+// Counted (tools/unit_list_count.py, profiles/unit_lists_notes.md): under a unit's masks a node keeps 1.43 children, so the walk
+// mostly steps down chains of inner nodes, each step a pop, a record load, a slab test and a table lookup.  device_tree.cpp proves
+// when such a step is redundant and applies it to all of a node's children up to 16 slots; per unit only the KEPT children matter.
+// The list of node N under the bounds B is built depth-first over kept children in ascending slot order:
+//   * a kept leaf child is an entry (its record index, node * slots + slot: what the walk loads when it pops the entry);
+//   * a kept inner child M none of whose children is kept is dropped: the walk would test M's box and then open nothing;
+//   * a kept inner child M is ABSORBED -- its kept children take its place, recursively -- when every kept child g of M is
+//     FP-nested in M's box as N's record states it (M.min <= g.min and g.max <= M.max per axis, on the floats the walk loads);
+//   * any other kept inner child is an entry; it gets a list of its own when a pass opens it.
+// Why absorbing is exact (device_tree.cpp's argument with "children" read as "children the unit keeps"; rays are inside B, so
+// neither walk visits a child that is not kept).  Let ray r be live in N's frame.  The mask walk tests g for r iff r passes M's
+// slab test when M is popped (t1(M) <= min(hi(M), best.t then)), and then tests g against best.t at g's pop.  IEEE subtraction and
+// multiplication by the ray's inverse direction are monotone, so g nested in M gives lo(M) <= lo(g) and hi(g) <= hi(M) per axis,
+// hence t1(M) <= t1(g) and hi(g) <= hi(M); best.t never grows, so best.t at g's pop <= best.t at M's pop.  A ray that passes g's
+// test, t1(g) <= min(hi(g), best.t at g's pop), therefore passes M's: testing g directly, for the rays live in N's frame, accepts
+// exactly the rays the two-step walk accepts, with the same limit.  Between M's pop and its children's pops the mask walk does
+// nothing else (M's frame goes on top), and the children of M stand where M stood, ascending, so a list walked last-to-first
+// visits the leaves in the mask walk's order: the same triangle tests in the same order, the same best.t throughout.
+// The arena: lists are appended and never freed; a list that does not fit resets the node table and the arena (the caller then
+// either builds it again or, if frames of the running walk still point into the arena, leaves that pass to a walk without a
+// cache).  Absorbing stops where the space left could not hold the entries still pending, each taken as one unexpanded entry.
+constexpr uint32_t kNullLink = 0xFFFFFFF8u;      // MP_LINK_NULL
+constexpr uint32_t kListOverflow = 0xFFFFFFFFu;  // unit_list_build: the list did not fit, table and arena were reset
+constexpr int kListDepth = 64;                   // continuation stack of the depth-first pass (lane registers)
+__device__ __forceinline__ uint32_t node_slot(uint32_t node) {
+    return min(node & static_cast<uint32_t>(kMaskCacheEntries - 1) & MP_NODE_SLOT_MASK, static_cast<uint32_t>(kMaskCacheEntries - 2));
+}
+// Every lane of the wave calls it.  recs: the walked tree, `slots` (8 or 16) records of 32 bytes per node; kept(b, bmn, bmx): the
+// unit's rejection test under the pattern of B (bounds_may_hit<OCT>).  Returns the table value of the list (first entry's dword
+// index << 16 | entries; no entries: nothing to open) after storing it under the node's tag, or kListOverflow.
+template <class Kept>
+__device__ __forceinline__ uint32_t unit_list_build(const float4* __restrict__ recs, uint32_t* mcache, uint32_t node, uint32_t slots, Kept kept) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const float* b = reinterpret_cast<const float*>(mcache);
+    node = __builtin_amdgcn_readfirstlane(node);  // (wave-uniform, which the arguments of a real call are not known to be)
+    slots = __builtin_amdgcn_readfirstlane(slots);
+    // lane j = child j of node n: its record and whether the unit keeps it
+    auto kept_of = [&](uint32_t n, float4& c0, float4& c1) -> uint32_t {
+        bool keep = false;
+        c0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f); c1 = c0;
+        if (lane < slots) {
+            const float4* r = recs + (static_cast<size_t>(n) * slots + lane) * 2;
+            c0 = r[0]; c1 = r[1];  // {min.xyz, max.x} {max.yz, link, n}
+            const float bmn[3] = {c0.x, c0.y, c0.z}, bmx[3] = {c0.w, c1.x, c1.y};
+            keep = as_u(c1.z) != kNullLink && kept(b, bmn, bmx);
+        }
+        return __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(__ballot(keep)));
+    };
+    float4 c0, c1;  // the records of `cur`, lane j = child j: a child's box and link are read from its lane, not loaded again
+    uint32_t mask = kept_of(node, c0, c1);
+    const uint32_t top = ~__builtin_amdgcn_readfirstlane(mcache[kArenaTopSlot]);
+    if (top > static_cast<uint32_t>(kArenaEntries) || top + static_cast<uint32_t>(__popc(mask)) > static_cast<uint32_t>(kArenaEntries)) {
+        MP_PROF_COUNT(5);
+        wave_lds_sync();
+#pragma unroll
+        for (int i = 0; i < (kMaskCacheEntries + 63) / 64; i++)
+            if (i * 64 + static_cast<int>(lane) < kMaskCacheEntries) mcache[kMaskCacheHeader + i * 64 + static_cast<int>(lane)] = 0xFFFFFFFFu;
+        wave_lds_sync();
+        return kListOverflow;
+    }
+    const uint32_t room = static_cast<uint32_t>(kArenaEntries) - top;
+    uint32_t used = 0u, pend = static_cast<uint32_t>(__popc(mask)), cur = node;  // invariant: used + pend <= room
+    int st_node = 0, st_mask = 0, depth = 0;  // (node, kept children still to take) of the nodes above `cur`: entry i in lane i
+    for (;;) {
+        if (mask == 0u) {
+            while (mask == 0u && depth > 0) {
+                depth--;
+                cur = static_cast<uint32_t>(__builtin_amdgcn_readlane(st_node, depth));
+                mask = static_cast<uint32_t>(__builtin_amdgcn_readlane(st_mask, depth));
+            }
+            if (mask == 0u) break;
+            if (lane < slots) {  // back at a node above: its records again
+                const float4* r = recs + (static_cast<size_t>(cur) * slots + lane) * 2;
+                c0 = r[0]; c1 = r[1];
+            }
+        }
+        const uint32_t j = static_cast<uint32_t>(__builtin_ctz(mask));
+        mask &= mask - 1u;
+        pend--;
+        const uint32_t rec = cur * slots + j;
+        auto from_lane = [&](float v) { return as_f(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(as_u(v)), static_cast<int>(j)))); };
+        const float4 p0 = make_float4(from_lane(c0.x), from_lane(c0.y), from_lane(c0.z), from_lane(c0.w));
+        const float4 p1 = make_float4(from_lane(c1.x), from_lane(c1.y), from_lane(c1.z), 0.0f);
+        const uint32_t link = as_u(p1.z);
+        bool emit = true;
+        if ((link & 63u) == 0u) {
+            const uint32_t m = link >> 6;
+            float4 g0, g1;
+            const uint32_t km = kept_of(m, g0, g1);
+            const bool sticks_out = ((km >> lane) & 1u) != 0u && lane < slots &&
+                                    !(p0.x <= g0.x && p0.y <= g0.y && p0.z <= g0.z && g0.w <= p0.w && g1.x <= p1.x && g1.y <= p1.y);
+            if (km == 0u) {
+                emit = false;
+            } else if (__ballot(sticks_out) == 0 && depth < kListDepth && used + pend + static_cast<uint32_t>(__popc(km)) <= room) {
+                if (mask != 0u) {
+                    // (v_writelane_b32 takes its lane select from M0 here, as the walk's frame stack does: one SGPR operand per VALU instruction)
+                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tv_writelane_b32 %0, %3, m0\n\tv_writelane_b32 %1, %4, m0"
+                                 : "+v"(st_node), "+v"(st_mask) : "s"(depth), "s"(__builtin_amdgcn_readfirstlane(cur)), "s"(__builtin_amdgcn_readfirstlane(mask)) : "m0");
+                    depth++;
+                }
+                cur = m; mask = km; pend += static_cast<uint32_t>(__popc(km));
+                c0 = g0; c1 = g1;
+                emit = false;
+            }
+        }
+        if (emit) {
+            if (lane == 0u) mcache[static_cast<uint32_t>(kArenaBase) + top + used] = rec;
+            used++;
+        }
+    }
+    const uint32_t val = ((static_cast<uint32_t>(kArenaBase) + top) << 16) | used;
+    if (lane == 0u) {
+        const uint32_t slot = node_slot(node);
+        mcache[static_cast<uint32_t>(kMaskCacheHeader) + slot] = node;
+        mcache[static_cast<uint32_t>(kNodeListBase) + slot] = val;
+        mcache[kArenaTopSlot] = ~(top + used);
+    }
+    wave_lds_sync();
+    return val;
 }
 
 // ---- ... and packet-level TRIANGLE rejection with the same bounds --------------------------------------------------------------------

@@ -621,6 +621,49 @@ __global__ void __launch_bounds__(256) unit_kernel(SamplerArg cam, float jitter_
     if (lane == 19u) out[kUnitOut * unit + 19u] = cleared;
 }
 
+// ---- (f) unit_list_build -------------------------------------------------------------------------------------------------------------
+// One wave per case (node, arena entries already in use): the cache starts with the case's header, every tag cleared and the
+// arena's fill set, and the wave calls the builder the walk calls, behind a real call as in the walk.  out[kListOut * case ..] =
+// returned value, arena entries in use afterwards, the tag and the value of the node's slot, then the whole arena.
+constexpr int kListOut = 4 + kArenaRoom;
+template <int OCT>
+__device__ __noinline__ uint32_t list_slow(const float4* __restrict__ recs, uint32_t* mcache, uint32_t node, uint32_t slots) {
+    return unit_list_build(recs, mcache, node, slots,
+                           [](const float* b, const float bmn[3], const float bmx[3]) { return bounds_may_hit<OCT>(b, bmn, bmx); });
+}
+__global__ void __launch_bounds__(256) list_kernel(const float4* recs, uint32_t slots, const uint32_t* headers, const uint32_t* cases, uint32_t n,
+                                                   uint32_t* out) {
+    __shared__ __align__(16) uint32_t lds[4 * kMaskCacheDwords];
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t c = blockIdx.x * 4u + w;
+    if (c >= n) return;  // (whole waves)
+    uint32_t* const base = lds + w * kMaskCacheDwords;
+    for (uint32_t i = lane; i < static_cast<uint32_t>(kMaskCacheDwords); i += 64u)
+        base[i] = i < static_cast<uint32_t>(kMaskCacheHeader) ? headers[32u * c + i] : i < static_cast<uint32_t>(kLeafMaskBase) ? 0xFFFFFFFFu : 0xDEAD0000u + i;
+    wave_lds_sync();
+    const uint32_t node = cases[2u * c], top0 = cases[2u * c + 1u];
+    if (lane == 0u) base[kArenaTopSlot] = ~top0;
+    wave_lds_sync();
+    uint32_t val;
+    switch (__builtin_amdgcn_readfirstlane(base[kHdrState]) & 7u) {
+        case 0: val = list_slow<0>(recs, base, node, slots); break;
+        case 1: val = list_slow<1>(recs, base, node, slots); break;
+        case 2: val = list_slow<2>(recs, base, node, slots); break;
+        case 3: val = list_slow<3>(recs, base, node, slots); break;
+        case 4: val = list_slow<4>(recs, base, node, slots); break;
+        case 5: val = list_slow<5>(recs, base, node, slots); break;
+        case 6: val = list_slow<6>(recs, base, node, slots); break;
+        default: val = list_slow<7>(recs, base, node, slots); break;
+    }
+    wave_lds_sync();
+    uint32_t* const o = out + static_cast<size_t>(c) * kListOut;
+    if (lane == 0u) {
+        const uint32_t slot = node_slot(node);
+        o[0] = val; o[1] = ~base[kArenaTopSlot]; o[2] = base[static_cast<uint32_t>(kMaskCacheHeader) + slot]; o[3] = base[static_cast<uint32_t>(kNodeListBase) + slot];
+    }
+    for (uint32_t i = lane; i < static_cast<uint32_t>(kArenaRoom); i += 64u) o[4u + i] = base[static_cast<uint32_t>(kArenaBase) + i];
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // One launch on a fresh counter buffer.  HIP's last-error state is per thread and sticky: an error that earlier work of the process
 // left there is not this probe's, so it is cleared before the launch, and every call's own status is checked (probe.hip).
@@ -769,5 +812,40 @@ int mp_mask_probe_pass(uint64_t seed, uint64_t nwaves, unsigned long long* out) 
     return run([&](unsigned long long* d) {
         hipLaunchKernelGGL(pass_kernel, dim3(static_cast<uint32_t>(nwaves / 4)), dim3(256), 0, 0, seed, d);
     }, out);
+}
+// (f) unit_list_build: the tree `recs` (n_nodes nodes of `slots` records of 8 dwords, as mp_scene_device_tree exports it; every inner
+// link must name a node of it), ncases headers of 32 dwords and cases {node, arena entries in use} -> mp_mask_probe_list_dwords()
+// dwords per case.  info (may be null): {arena entries, node table entries, dword index of the arena's first entry}.  Returns -1 for
+// a case outside the tree or the arena.
+int mp_mask_probe_list_dwords() { return kListOut; }
+int mp_mask_probe_list(const uint32_t* recs, uint32_t n_nodes, uint32_t slots, const uint32_t* headers, const uint32_t* cases, uint32_t ncases,
+                       uint32_t* out, uint32_t* info) {
+    (void)hipGetLastError();
+    if (info) { info[0] = static_cast<uint32_t>(kArenaEntries); info[1] = static_cast<uint32_t>(kMaskCacheEntries); info[2] = static_cast<uint32_t>(kArenaBase); }
+    if (slots != 8u && slots != 16u) return -1;
+    for (uint32_t c = 0; c < ncases; c++)
+        if (cases[2u * c] >= n_nodes || cases[2u * c + 1u] > static_cast<uint32_t>(kArenaEntries)) return -1;
+    for (size_t i = 0; i < static_cast<size_t>(n_nodes) * slots; i++) {
+        const uint32_t link = recs[i * 8u + 6u];
+        if (link != kNullLink && (link & 63u) == 0u && (link >> 6) >= n_nodes) return -1;
+    }
+    if (ncases == 0u) return 0;
+    uint32_t *drecs = nullptr, *dhdr = nullptr, *dcases = nullptr, *dout = nullptr;
+    const size_t rec_bytes = sizeof(uint32_t) * 8u * slots * n_nodes, out_bytes = sizeof(uint32_t) * kListOut * static_cast<size_t>(ncases);
+    hipError_t e = hipMalloc(&drecs, rec_bytes);
+    if (e == hipSuccess) e = hipMalloc(&dhdr, sizeof(uint32_t) * 32u * ncases);
+    if (e == hipSuccess) e = hipMalloc(&dcases, sizeof(uint32_t) * 2u * ncases);
+    if (e == hipSuccess) e = hipMalloc(&dout, out_bytes);
+    if (e == hipSuccess) e = hipMemcpy(drecs, recs, rec_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dhdr, headers, sizeof(uint32_t) * 32u * ncases, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dcases, cases, sizeof(uint32_t) * 2u * ncases, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(list_kernel, dim3((ncases + 3u) / 4u), dim3(256), 0, 0, reinterpret_cast<const float4*>(drecs), slots, dhdr, dcases, ncases, dout);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, dout, out_bytes, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(drecs); (void)hipFree(dhdr); (void)hipFree(dcases); (void)hipFree(dout);
+    return static_cast<int>(e);
 }
 }

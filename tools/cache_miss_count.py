@@ -17,13 +17,15 @@ else:
 fr = mp.FrameRenderer(scene, cam, mp.RenderSettings(64, spp, (1920, 1080), seed=0x5EED))
 fr.render(); torch.cuda.synchronize()
 lib = _lib.lib()
-out = (C.c_ulonglong * 4)()
-lib.mp_prof_read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
-assert lib.mp_prof_read(out, 1) == 0
+out = (C.c_ulonglong * 8)()
+read = lib.mp_prof_read8 if hasattr(lib, "mp_prof_read8") else lib.mp_prof_read  # (a library from before the child lists: four counters)
+read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+assert read(out, 1) == 0
 fr.render(); torch.cuda.synchronize()
-assert lib.mp_prof_read(out, 0) == 0
+assert read(out, 0) == 0
 S = 16 if spp >= 64 else 8 if spp >= 32 else 4
 units = 1920 * 1080 // (64 // S)
 passes = units * (spp // S)
-print(f"{which} x{spp}: per unit: node-mask slow paths {out[0] / units:.1f}, leaf-mask slow paths {out[1] / units:.1f}, bounds (re)set {out[3] / units:.2f};"
-      f" per pass: node visits {out[2] / passes:.1f}")
+print(f"{which} x{spp}: per unit: node-list slow paths {out[0] / units:.1f}, leaf-mask slow paths {out[1] / units:.1f}, bounds (re)set {out[3] / units:.2f};"
+      f" per pass: node visits (inner links followed) {out[2] / passes:.2f}")
+print(f"{which} x{spp}: per unit: node-table evictions {out[4] / units:.3f}, arena resets {out[5] / units:.4f}; passes left to the uncached walk: {out[6]} of {passes}")
