@@ -229,7 +229,7 @@ int mp_ctx_set_option(mp_ctx *ctx, const char *key, int value);
  * mp_render_pass_multi) whose shard travelled through pinned host memory. */
 int mp_ctx_query(mp_ctx *ctx, const char *key, uint64_t *value);
 /* Diagnostics.  The kernels launched by the last call on ctx that launched any (mp_render_tile, mp_render_tiles_device*,
- * mp_render_aov_device, mp_untile*, mp_trace_rays*, mp_occluded_rays, mp_generate_rays; one call = one record, so mp_render_tile
+ * mp_render_aov_device, mp_render_aov_pass_device, mp_untile*, mp_trace_rays*, mp_occluded_rays, mp_generate_rays; one call = one record, so mp_render_tile
  * reports its render kernel only, and mp_render_tiles_device_ex with d_ray_segments the counter's set_u64_kernel before the render
  * kernel): the kernels' names with their template arguments as the library's kernel table writes them, e.g.
  * "render_tiles_packet_kernel<16, false, 8, false, true>", distinct names in launch order, separated by '\n' (the staged path
@@ -436,6 +436,46 @@ typedef struct {
 int mp_render_aov_device(mp_ctx *ctx, const mp_scene *scene, const mp_camera_sampler *sampler, const mp_settings *settings,
                          const mp_block *tiles, size_t n_tiles, const mp_aov_planes *planes, const mp_launch_extras *extras,
                          void *stream);
+/* The feature planes in progressive passes, plus the hit point and the second moment of the shade.  BUILD-DEFINED, a superset of
+ * mp_render_aov_device (which keeps its behaviour, its refusals included): the same rays, the same one rule per float channel
+ * (acc = +0.0; acc = acc + (hit ? value : +0.0) in sample-index order; pixel = acc * (1.0f / (float)sample_count)), the same
+ * layout, and any plane may be NULL.
+ *   d_shade, d_normal, d_albedo, d_ids : as in mp_aov_planes, bit for bit.
+ *   d_position : {p.x, p.y, p.z, alpha}: value = HitRecord.point as mp_trace_rays reports it, point_at(t) of the WORLD ray
+ *                (o + d * t per coordinate, one rounded product and one rounded sum; in object groups not the member's ray).
+ *   d_shade_sq : {q, q, q, alpha}: value = fl(c * c), ONE rounded f32 product (no contraction) of the f32 shade value c = |d . n|
+ *                that d_shade adds.  With d_shade it gives the per-pixel variance of the shade; it is not d_shade squared.
+ * struct_size = sizeof(mp_aov_planes_ex) of the caller (members beyond it are not read); smaller than the struct as first
+ * published (through d_shade_sq): MP_ERR_INVALID.  mp_aov_planes_ex_size() is the library's own.
+ * Passes.  settings->flags & MP_FLAG_ACCUMULATE with pass_begin / pass_count means exactly what it means for
+ * mp_render_tiles_device: the launch adds samples [pass_begin, pass_end) (pass_count == 0: through sample_count - 1) on top of the
+ * state the planes hold, pass_begin == 0 starts from zeros whatever the planes hold, and the pass that reaches sample_count writes
+ * the means.  Without the flag the call is the whole frame in one launch.
+ * State between passes, per plane and self-contained:  d_shade, d_albedo, d_position, d_shade_sq hold {sum, sum, sum, hit count}
+ * (their three sums each), d_normal holds {sum n.x, sum n.y, sum n.z, sum t} -- so d_shade's state is bit for bit the state
+ * mp_render_tiles_device keeps in its tile buffer under MP_FLAG_ACCUMULATE with the reference semantics, and mp_untile_preview
+ * works on every float plane as it is.  The hit count a pass continues from is read from the first non-NULL of d_shade, d_albedo,
+ * d_position, d_shade_sq (a launch with only d_normal and / or d_ids needs none).  THE CALLER'S CONTRACT: the same set of planes,
+ * the same settings but for the pass and the same tiles on every pass of a frame, pass_begin = the previous pass's end.
+ * d_ids is written only by the pass that contains sample 0; later passes do not touch it.
+ * Any split of [0, sample_count) into passes gives the bits of the single launch, for every plane.
+ * MP_FLAG_CHUNKED_SUM, MP_FLAG_WAVEFRONT, MP_FLAG_TRAVERSAL_GROUPS: MP_ERR_UNSUPPORTED.  A pass outside [0, sample_count), a bad
+ * struct_size: MP_ERR_INVALID.  A refused call launches nothing and writes nothing.  All planes NULL, or n_tiles == 0: a no-op
+ * returning MP_OK.  MP_FLAG_PATHS / max_depth: accepted and ignored.  `extras` (nullable): tile_order and d_tile_cost as in
+ * mp_render_tiles_device_ex; *d_ray_segments receives pixels * samples of the pass. */
+typedef struct {
+    uint32_t  struct_size;  /* sizeof(mp_aov_planes_ex) of the caller                                  */
+    float    *d_shade;      /* as mp_aov_planes                                                        */
+    float    *d_normal;
+    float    *d_albedo;
+    uint32_t *d_ids;
+    float    *d_position;   /* {p.x, p.y, p.z, alpha}: HitRecord.point, point_at(t) of the world ray   */
+    float    *d_shade_sq;   /* {q, q, q, alpha}: q from fl(c * c), c the f32 shade value of d_shade    */
+} mp_aov_planes_ex;
+int mp_render_aov_pass_device(mp_ctx *ctx, const mp_scene *scene, const mp_camera_sampler *sampler, const mp_settings *settings,
+                              const mp_block *tiles, size_t n_tiles, const mp_aov_planes_ex *planes,
+                              const mp_launch_extras *extras, void *stream);
+uint32_t mp_aov_planes_ex_size(void);  /* sizeof(mp_aov_planes_ex) in this library */
 /* machinery.rs:78-89 (tile buffer -> image copy) on the device: scatters tile-major tiles into an image-major
  * f32 frame and/or its color_to_image u8 frame (either may be NULL). */
 int mp_untile(mp_ctx *ctx, const mp_settings *settings, const mp_block *tiles, size_t n_tiles,

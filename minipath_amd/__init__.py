@@ -4,7 +4,7 @@ Host-side mirror of the reference's public API (src/lib.rs:8-10): ``render``, ``
 ``RenderSettings``, ``Camera``, ``Scene`` and ``TriangleBvh``, over the C ABI of ``include/minipath_hip.h``.
 All compute happens in ``csrc/libminipath_hip.so`` (hand-written HIP kernels); there is no CPU path here.
 """
-from ._lib import AovPlanes, MinipathError, MP_NO_PRIM, MP_LINK_NULL, MAX_MATERIALS, SO_PATH  # noqa: F401
+from ._lib import AovPlanes, AovPlanesEx, MinipathError, MP_NO_PRIM, MP_LINK_NULL, MAX_MATERIALS, SO_PATH  # noqa: F401
 from .camera import Camera, CameraSampler  # noqa: F401
 from .screen_block import ScreenBlock, tile_ordering  # noqa: F401
 from .scene import Context, Instances, ObjectGroup, Scene, Sphere, TriangleBvh  # noqa: F401
@@ -12,7 +12,7 @@ from .renderer import (RenderProgress, RenderProgressSnapshot, RenderSettings, r
                        FrameRenderer, MultiDeviceFrame)
 
 __all__ = [
-    "AovPlanes", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
+    "AovPlanes", "AovPlanesEx", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
     "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "Sphere", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]

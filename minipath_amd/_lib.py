@@ -179,6 +179,13 @@ class AovPlanes(C.Structure):
     _fields_ = [("d_shade", C.c_void_p), ("d_normal", C.c_void_p), ("d_albedo", C.c_void_p), ("d_ids", C.c_void_p)]
 
 
+class AovPlanesEx(C.Structure):
+    """mp_aov_planes_ex: the planes of mp_render_aov_pass_device (struct_size first; any plane may be NULL)."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("d_shade", C.c_void_p), ("d_normal", C.c_void_p), ("d_albedo", C.c_void_p), ("d_ids", C.c_void_p),
+                ("d_position", C.c_void_p), ("d_shade_sq", C.c_void_p)]
+
+
 STARTED_CB = C.CFUNCTYPE(None, C.c_void_p, Block)
 FINISHED_CB = C.CFUNCTYPE(None, C.c_void_p, Block, Progress)
 
@@ -250,6 +257,12 @@ SIGNATURES = {
         [C.c_void_p, C.c_void_p, C.POINTER(SamplerStruct), C.POINTER(SettingsStruct), C.POINTER(Block), C.c_size_t,
          C.POINTER(AovPlanes), C.POINTER(LaunchExtras), C.c_void_p],
     ),
+    "mp_render_aov_pass_device": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.POINTER(SamplerStruct), C.POINTER(SettingsStruct), C.POINTER(Block), C.c_size_t,
+         C.POINTER(AovPlanesEx), C.POINTER(LaunchExtras), C.c_void_p],
+    ),
+    "mp_aov_planes_ex_size": (C.c_uint32, []),
     "mp_untile": (
         C.c_int,
         [C.c_void_p, C.POINTER(SettingsStruct), C.POINTER(Block), C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -1229,20 +1230,15 @@ int mp_render_tiles_device_ex(mp_ctx* ctx, const mp_scene* scene, const mp_camer
     });
 }
 
-// First-hit feature planes (build-defined, include/minipath_hip.h): validation as mp_render_tiles_device_ex, one launch.
-int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* sampler, const mp_settings* settings,
-                         const mp_block* tiles, size_t n_tiles, const mp_aov_planes* planes, const mp_launch_extras* extras,
-                         void* stream) {
-    return guarded([&]() -> int {
-    if (!ctx || !scene || !sampler || !planes || !settings) return fail(MP_ERR_INVALID, "bad argument");
-    if (settings->flags & (MP_FLAG_ACCUMULATE | MP_FLAG_CHUNKED_SUM))
-        return fail(MP_ERR_UNSUPPORTED, "the feature planes are written by one launch over all samples: MP_FLAG_ACCUMULATE / MP_FLAG_CHUNKED_SUM are not supported");
-    if (settings->flags & (MP_FLAG_WAVEFRONT | MP_FLAG_TRAVERSAL_GROUPS))
-        return fail(MP_ERR_UNSUPPORTED, "the feature planes run on the packet walk: MP_FLAG_WAVEFRONT / MP_FLAG_TRAVERSAL_GROUPS are not supported");
+// First-hit feature planes (build-defined, include/minipath_hip.h): validation as mp_render_tiles_device_ex, one launch.  What the
+// two entry points share, after their refusals by flag: the pass of the settings (the whole frame without MP_FLAG_ACCUMULATE).
+static int render_aov_planes(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* sampler, const mp_settings* settings,
+                             const mp_block* tiles, size_t n_tiles, const mp_aov_planes_ex* planes, const mp_launch_extras* extras,
+                             void* stream) {
     if (!valid_settings(settings)) return fail(MP_ERR_INVALID, "bad argument");
     if (n_tiles && !tiles) return fail(MP_ERR_INVALID, "NULL tiles");
     if (scene->ctx != ctx) return fail(MP_ERR_INVALID, "scene belongs to another context");
-    if (n_tiles == 0 || !(planes->d_shade || planes->d_normal || planes->d_albedo || planes->d_ids)) return MP_OK;
+    if (n_tiles == 0 || !(planes->d_shade || planes->d_normal || planes->d_albedo || planes->d_ids || planes->d_position || planes->d_shade_sq)) return MP_OK;
     if (n_tiles > 0xFFFFFFFFull) return fail(MP_ERR_INVALID, "too many tiles");
     uint64_t* d_ray_segments = extras ? extras->d_ray_segments : nullptr;
     const uint32_t* tile_order = extras ? extras->tile_order : nullptr;
@@ -1252,7 +1248,7 @@ int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sam
         if (!(t.min_x < t.max_x && t.min_y < t.max_y) || t.max_x - t.min_x > settings->tile_size ||
             t.max_y - t.min_y > settings->tile_size || t.max_x > settings->width || t.max_y > settings->height)
             return fail(MP_ERR_INVALID, "tile empty, larger than tile_size, or outside the resolution");
-        rays += static_cast<uint64_t>(t.max_x - t.min_x) * (t.max_y - t.min_y) * settings->sample_count;
+        rays += static_cast<uint64_t>(t.max_x - t.min_x) * (t.max_y - t.min_y) * pass_samples(*settings);
     }
     if (tile_order) {  // must be a permutation: every tile is rendered exactly once
         std::vector<bool> seen(n_tiles, false);
@@ -1297,13 +1293,47 @@ int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sam
     L.d_segments = nullptr;
     L.d_tile_order = d_order;
     L.d_tile_cost = reinterpret_cast<unsigned long long*>(extras ? extras->d_tile_cost : nullptr);
-    L.pass_begin = 0;
-    L.pass_end = settings->sample_count;
+    L.pass_begin = (settings->flags & MP_FLAG_ACCUMULATE) ? settings->pass_begin : 0u;  // as render_tiles_device derives them
+    L.pass_end = L.pass_begin + pass_samples(*settings);
+    L.carry_in = L.pass_begin > 0;
+    L.finalize = L.pass_end == settings->sample_count;
+    L.aov_wide_park = planes->d_position || planes->d_shade_sq;
     rc = launch_render_aov(L, *planes, stream, err);
     if (rc) return fail(rc, err);
     return MP_OK;
+}
+
+int mp_render_aov_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* sampler, const mp_settings* settings,
+                         const mp_block* tiles, size_t n_tiles, const mp_aov_planes* planes, const mp_launch_extras* extras,
+                         void* stream) {
+    return guarded([&]() -> int {
+    if (!ctx || !scene || !sampler || !planes || !settings) return fail(MP_ERR_INVALID, "bad argument");
+    if (settings->flags & (MP_FLAG_ACCUMULATE | MP_FLAG_CHUNKED_SUM))
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes are written by one launch over all samples: MP_FLAG_ACCUMULATE / MP_FLAG_CHUNKED_SUM are not supported");
+    if (settings->flags & (MP_FLAG_WAVEFRONT | MP_FLAG_TRAVERSAL_GROUPS))
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes run on the packet walk: MP_FLAG_WAVEFRONT / MP_FLAG_TRAVERSAL_GROUPS are not supported");
+    const mp_aov_planes_ex pl{static_cast<uint32_t>(sizeof(mp_aov_planes_ex)), planes->d_shade, planes->d_normal, planes->d_albedo, planes->d_ids, nullptr, nullptr};
+    return render_aov_planes(ctx, scene, sampler, settings, tiles, n_tiles, &pl, extras, stream);
     });
 }
+
+// The planes in progressive passes, with the point and the squared shade (build-defined, include/minipath_hip.h)
+int mp_render_aov_pass_device(mp_ctx* ctx, const mp_scene* scene, const mp_camera_sampler* sampler, const mp_settings* settings,
+                              const mp_block* tiles, size_t n_tiles, const mp_aov_planes_ex* planes, const mp_launch_extras* extras,
+                              void* stream) {
+    return guarded([&]() -> int {
+    if (!ctx || !scene || !sampler || !planes || !settings) return fail(MP_ERR_INVALID, "bad argument");
+    if (planes->struct_size < offsetof(mp_aov_planes_ex, d_shade_sq) + sizeof(float*))
+        return fail(MP_ERR_INVALID, "mp_aov_planes_ex.struct_size is smaller than the struct through d_shade_sq");
+    if (settings->flags & MP_FLAG_CHUNKED_SUM)
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes keep plain f32 sums between passes: MP_FLAG_CHUNKED_SUM is not supported");
+    if (settings->flags & (MP_FLAG_WAVEFRONT | MP_FLAG_TRAVERSAL_GROUPS))
+        return fail(MP_ERR_UNSUPPORTED, "the feature planes run on the packet walk: MP_FLAG_WAVEFRONT / MP_FLAG_TRAVERSAL_GROUPS are not supported");
+    return render_aov_planes(ctx, scene, sampler, settings, tiles, n_tiles, planes, extras, stream);
+    });
+}
+
+uint32_t mp_aov_planes_ex_size(void) { return static_cast<uint32_t>(sizeof(mp_aov_planes_ex)); }
 
 int mp_untile(mp_ctx* ctx, const mp_settings* settings, const mp_block* tiles, size_t n_tiles, const float* d_tiles_f32,
               float* d_image_f32, uint8_t* d_image_u8, void* stream) {

@@ -175,21 +175,24 @@ LaunchPlan plan_render_tiles(const RenderLaunch& L) {
     return p;
 }
 
-// mp_render_aov_device: the packet kernel with feature planes (render_aov_packet_kernel).  Samples in flight and mask cache follow
-// plan_render_tiles' facts on a shorter list of instantiations: S = 16 from 16 samples per pixel on, 4 from 4 on, else 1;
-// with the mask cache (same cache_ok; units of at least four passes) 16 from 64 samples on and 4 for 16-63; object groups and
-// LDS-stack scenes 16 or 1.  A packet_samples_in_flight request is rounded down to these.
+// mp_render_aov_device / mp_render_aov_pass_device: the packet kernel with feature planes (render_aov_packet_kernel).  Samples in
+// flight and mask cache follow plan_render_tiles' facts on a shorter list of instantiations, by the samples per pixel of THIS
+// launch (a pass of a progressive frame: pass_end - pass_begin, as plan_render_tiles; the whole frame: spp): S = 16 from 16 samples
+// on, 4 from 4 on, else 1; with the mask cache (same cache_ok; units of at least four passes) 16 from 64 samples on and 4 for 16-63;
+// object groups and LDS-stack scenes 16 or 1.  A packet_samples_in_flight request is rounded down to these.  The parked sums take
+// 32 bytes per pixel, 48 with the point or the squared shade (aov_wide_park).
 LaunchPlan plan_render_aov(const RenderLaunch& L) {
     const PacketFacts f = packet_facts(L);
     LaunchPlan p;
-    const uint32_t nspp = L.spp;
+    const uint32_t nspp = L.pass_end - L.pass_begin;  // samples per pixel in this launch
     int S = nspp >= 16 ? 16 : nspp >= 4 ? 4 : 1;
     if (f.cache_ok && nspp >= 16) S = nspp >= 64 ? 16 : 4;
     if (L.packet_samples) S = L.packet_samples >= 16u ? 16 : L.packet_samples >= 4u ? 4 : 1;
     if ((f.obj || f.lds_stack) && S == 4) S = 1;
     const bool mcache = f.cache_ok && S >= 4 && nspp >= 4u * static_cast<uint32_t>(S);
     p.lds_per_wave = f.stack_lds_per_wave;
-    const uint32_t park = 4u * (64u / static_cast<uint32_t>(S)) * 32u;  // the parked sums of the block's four waves
+    p.park_pixel = L.aov_wide_park ? 48u : 32u;
+    const uint32_t park = 4u * (64u / static_cast<uint32_t>(S)) * p.park_pixel;  // the parked sums of the block's four waves
     p.lds = park + (mcache ? 4u * kPlanMaskCacheDwords * 4u : p.lds_per_wave * 4u);
     if (p.lds > kLdsPerCu) return refuse<LaunchPlan>(kTooDeepStack);
     p.grid = static_cast<uint32_t>(std::min<uint64_t>(f.want * S, static_cast<uint64_t>(L.cu_count) * blocks_per_cu(p.lds)));

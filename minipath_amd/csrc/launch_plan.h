@@ -30,6 +30,7 @@ struct LaunchPlan {
     uint32_t pool_stride = 0;      // pooled path kernel: floats per wave, and the bytes of the whole pool
     size_t pool_bytes = 0;
     uint64_t units2 = 0;           // two rays per lane: 8-pixel work units of the launch
+    uint32_t park_pixel = 0;       // feature planes: bytes of parked sums per pixel (32, or 48 with RenderLaunch::aov_wide_park)
 };
 
 // Staged path evaluation.  A batch is tb tiles x sc samples; the last batch of a launch may hold fewer tiles.

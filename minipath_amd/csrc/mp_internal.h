@@ -189,14 +189,16 @@ struct RenderLaunch {
     uint32_t rays_per_lane = 1;   // 2: 128-ray walks (render_tiles_packet2_kernel) where applicable
     uint32_t mask_cache = 1;      // packet kernel: per-unit mask cache of the packet-level child / triangle rejection: 0 off, 1 / 2 on (units of >= 4 passes)
     uint32_t paths_pooled = 1;    // path extension: 0 = one pass per walk (render_paths_kernel), 1 = pooled passes for big scenes (auto), 2 / 3 = always pooled (two / up to four passes)
+    bool aov_wide_park = false;   // feature planes: d_position or d_shade_sq is asked for, 48 bytes of parked sums per pixel instead of 32
     const uint32_t* d_tile_order = nullptr;      // optional: hand-out order of the tiles (device, n_tiles)
     unsigned long long* d_tile_cost = nullptr;   // optional: += shader-clock cycles spent per tile (device, n_tiles)
 };
 
 int launch_render_tiles(const RenderLaunch& L, void* stream, std::string& err);
 int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::string& err);
-// mp_render_aov_device: the packet render with feature planes (L.d_out, the pass range and the path fields are not read)
-int launch_render_aov(const RenderLaunch& L, const mp_aov_planes& planes, void* stream, std::string& err);
+// mp_render_aov_device / mp_render_aov_pass_device: the packet render with feature planes (L.d_out and the path fields are not read;
+// planes.struct_size is not read either)
+int launch_render_aov(const RenderLaunch& L, const mp_aov_planes_ex& planes, void* stream, std::string& err);
 int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx,
                       const float* dy, const float* dz, uint64_t n, const mp_hits_soa& hits, int cu_count, void* stream,
                       std::string& err);

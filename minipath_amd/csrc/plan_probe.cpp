@@ -6,6 +6,11 @@
 
 using namespace mp;
 
+struct mp_plan_in;
+struct mp_plan_out;
+// one plan into *out; *park_pixel (nullable): LaunchPlan::park_pixel
+static void plan_into(int api, const mp_plan_in* in, uint64_t n_rays, bool aov_wide_park, mp_plan_out* out, uint32_t* park_pixel = nullptr);
+
 extern "C" {
 
 // the fields of RenderLaunch / DevScene a plan reads
@@ -31,8 +36,18 @@ int mp_plan_kernel_count() { return K_COUNT; }
 const char* mp_plan_kernel_name(int id) { return id >= 0 && id < K_COUNT ? kKernelNames[id] : nullptr; }
 
 // api: 0 render tiles, 1 feature planes, 2 staged paths, 3 / 4 / 5 mp_trace_rays / bounded / occluded with n_rays rays
-void mp_plan(int api, const mp_plan_in* in, uint64_t n_rays, mp_plan_out* out) {
+void mp_plan(int api, const mp_plan_in* in, uint64_t n_rays, mp_plan_out* out) { plan_into(api, in, n_rays, false, out); }
+
+// the feature planes of mp_render_aov_pass_device: the pass [pass_begin, pass_end) of `in`; wide_park != 0: d_position or d_shade_sq
+// is asked for.  *park_pixel (nullable) receives the bytes of parked sums per pixel.
+void mp_plan_aov_pass(const mp_plan_in* in, int wide_park, mp_plan_out* out, uint32_t* park_pixel) {
+    plan_into(1, in, 0, wide_park != 0, out, park_pixel);
+}
+}
+
+static void plan_into(int api, const mp_plan_in* in, uint64_t n_rays, bool aov_wide_park, mp_plan_out* out, uint32_t* park_pixel) {
     RenderLaunch L{};
+    L.aov_wide_park = aov_wide_park;
     L.scene.kind = in->kind;
     L.scene.inst_count = in->inst_count;
     L.scene.inner_count = in->inner_count;
@@ -77,7 +92,7 @@ void mp_plan(int api, const mp_plan_in* in, uint64_t n_rays, mp_plan_out* out) {
         error = p.error;
         out->kernel = p.kernel; out->grid = p.grid; out->lds = p.lds; out->lds_per_wave = p.lds_per_wave;
         out->pool_stride = p.pool_stride; out->pool_bytes = p.pool_bytes; out->units2 = p.units2;
+        if (park_pixel) *park_pixel = p.park_pixel;
     }
     if (error) std::strncpy(out->error, error, sizeof(out->error) - 1);
-}
 }

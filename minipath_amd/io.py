@@ -108,7 +108,9 @@ def save_exr_layers(path: str, layers: dict) -> None:
     32-bit-float scanline OpenEXR file.  `layers` maps a name to an [h, w] array (one channel of that name) or an [h, w, k] array
     with k <= 4 (channels name.R, name.G, name.B, name.A -- or name.X, name.Y, name.Z for the names "N" and "normal"); all of
     one size.  Channels are stored sorted by name (byte order), as EXR requires; the values survive bit for bit.  Example:
-    save_exr_layers(p, {"N": nxyz, "Z": t, "albedo": rgb, "A": alpha}); load_exr_f32(p, layers=True) reads it back."""
+    save_exr_layers(p, {"N": nxyz, "Z": t, "albedo": rgb, "A": alpha}); load_exr_f32(p, layers=True) reads it back.  The planes
+    of FrameRenderer.render_aov_pass go the same way: {"P": position[..., :3]} gives P.R, P.G, P.B (x, y, z), and
+    {"shade_sq": q[..., 0]} one channel of that name."""
     chans = {}
     for name, arr in layers.items():
         a = np.asarray(arr)
@@ -183,17 +185,28 @@ def _settings_key(settings) -> np.ndarray:
                     dtype=np.uint64)
 
 
-def save_checkpoint(path: str, renderer, next_sample: int) -> None:
+_PLANE_PREFIX = "plane_"  # npz member of a feature plane
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def save_checkpoint(path: str, renderer, next_sample: int, planes=None) -> None:
     """Dump a FrameRenderer's running per-pixel sums (tile-major f32 RGBA: rgb = sequential sample sum, a = hit count) and the
-    index of the next sample to draw, after render_pass().  Plain .npz (no pickle)."""
+    index of the next sample to draw, after render_pass().  Plain .npz (no pickle).  planes: the dict of
+    FrameRenderer.render_aov_pass() (name -> tile-major tensor or array), stored beside the sums with its dtypes."""
     tiles = np.array([[t.min_x, t.min_y, t.max_x, t.max_y] for t in renderer.tiles], dtype=np.uint32).reshape(-1, 4)
-    np.savez(path, sums=renderer.tile_buf.detach().cpu().numpy(), next_sample=np.uint32(next_sample),
-             settings=_settings_key(renderer.settings), tiles=tiles)
+    extra = {_PLANE_PREFIX + str(k): _host(v) for k, v in (planes or {}).items()}
+    np.savez(path, sums=_host(renderer.tile_buf), next_sample=np.uint32(next_sample),
+             settings=_settings_key(renderer.settings), tiles=tiles, **extra)
 
 
-def load_checkpoint(path: str, renderer) -> int:
+def load_checkpoint(path: str, renderer, planes=None) -> int:
     """Restore the sums into `renderer.tile_buf` and return the next sample index.  The renderer must have been built for the
-    same settings and tile list (the sample streams are keyed by them)."""
+    same settings and tile list (the sample streams are keyed by them).  planes: a dict of fresh planes
+    (FrameRenderer.new_aov_planes) that receives the stored ones; it must name exactly the planes the checkpoint holds, with
+    their shapes and dtypes (the passes of a frame take the same set of planes).  Nothing is restored when a check fails."""
     import torch
 
     with np.load(path, allow_pickle=False) as z:
@@ -205,5 +218,19 @@ def load_checkpoint(path: str, renderer) -> int:
         sums = z["sums"]
         if tuple(sums.shape) != tuple(renderer.tile_buf.shape):
             raise ValueError("checkpoint buffer shape differs")
+        if planes is not None:
+            stored = {n[len(_PLANE_PREFIX):] for n in z.files if n.startswith(_PLANE_PREFIX)}
+            if stored != {str(k) for k in planes}:
+                raise ValueError(f"checkpoint holds the planes {sorted(stored)}, not {sorted(str(k) for k in planes)}")
+            for k, dst in planes.items():
+                src = z[_PLANE_PREFIX + str(k)]
+                if tuple(src.shape) != tuple(dst.shape) or src.dtype != _host(dst[:0]).dtype:
+                    raise ValueError(f"checkpoint plane {k!r}: shape or dtype differs")
+        for k, dst in (planes or {}).items():
+            src = np.ascontiguousarray(z[_PLANE_PREFIX + str(k)])
+            if isinstance(dst, np.ndarray):
+                dst[...] = src
+            else:
+                dst.copy_(torch.from_numpy(src))
         renderer.tile_buf.copy_(torch.from_numpy(np.ascontiguousarray(sums)))
         return int(z["next_sample"])

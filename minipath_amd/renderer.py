@@ -332,13 +332,58 @@ class FrameRenderer:
         )
         return out
 
-    def untile_plane(self, plane):
-        """A tile-major plane of render_aov() -> image-major [h, w, 4] of the same dtype.  The scatter moves the 16-byte pixels'
-        bit patterns untouched, so the int32 "ids" plane goes through the float path as a view."""
+    AOV_PLANES = ("shade", "normal", "albedo", "ids", "position", "shade_sq")  # the members of mp_aov_planes_ex, in its order
+
+    def new_aov_planes(self, shade: bool = True, normal: bool = True, albedo: bool = True, ids: bool = True, position: bool = False,
+                       shade_sq: bool = False) -> dict:
+        """Zeroed tile-major tensors shaped like `tile_buf` for render_aov_pass(): the planes of render_aov(), plus "position"
+        {p.x, p.y, p.z, alpha} (the world-space hit point, HitRecord.point) and "shade_sq" {q, q, q, alpha} (the second moment
+        of the shade: the sum of fl(c * c) over the samples * 1/spp; with "shade" it gives the per-pixel variance).  float32, "ids"
+        int32."""
+        import torch
+
+        ts = self.settings.tile_size
+        shape = (max(len(self.tiles), 1), ts, ts, 4)
+        want = dict(zip(self.AOV_PLANES, (shade, normal, albedo, ids, position, shade_sq)))
+        return {k: torch.zeros(shape, dtype=torch.int32 if k == "ids" else torch.float32, device=self.device) for k in self.AOV_PLANES if want[k]}
+
+    def render_aov_pass(self, planes: dict, begin: int = 0, count: int = 0) -> int:
+        """The feature planes in progressive passes (mp_render_aov_pass_device), mirroring render_pass(): adds samples
+        [begin, begin+count) of settings.sample_count (count 0 = through the last) on top of the running sums `planes` (a dict of
+        new_aov_planes(); the same dict on every pass of a frame) holds from the earlier passes, and returns the next sample
+        index.  begin=0, count=0 is the whole frame in one launch.  Between passes a float plane holds {sum, sum, sum, hit
+        count} ("normal": {sum n, sum t}): untile_plane(p, preview_samples=k) shows it after k samples; the pass that reaches
+        sample_count leaves the means.  "ids" is written by the pass that holds sample 0.  Any split gives the bits of the single
+        launch.  `planes` + the returned index is the checkpoint (io.save_checkpoint(..., planes=planes))."""
+        total = int(self.settings.sample_count)
+        if not (0 <= begin < total) or count < 0 or begin + count > total:
+            raise ValueError("pass outside [0, sample_count)")
+        unknown = set(planes) - set(self.AOV_PLANES)
+        if unknown:
+            raise ValueError(f"unknown planes: {sorted(unknown)}")
+        st = _lib.SettingsStruct.from_buffer_copy(self._st)
+        st.flags |= _lib.MP_FLAG_ACCUMULATE
+        st.pass_begin, st.pass_count = int(begin), int(count)
+        pl = _lib.AovPlanesEx(C.sizeof(_lib.AovPlanesEx), *[planes[k].data_ptr() if k in planes else None for k in self.AOV_PLANES])
+        _lib.check(
+            _lib.lib().mp_render_aov_pass_device(
+                self.ctx.handle, self.scene.object.handle, C.byref(self._sampler), C.byref(st), self._tiles_c,
+                len(self.tiles), C.byref(pl), C.byref(self._extras), self._stream(),
+            )
+        )
+        return total if count == 0 else begin + count
+
+    def untile_plane(self, plane, preview_samples: Optional[int] = None):
+        """A tile-major plane of render_aov() / render_aov_pass() -> image-major [h, w, 4] of the same dtype.  The scatter moves
+        the 16-byte pixels' bit patterns untouched, so the int32 "ids" plane goes through the float path as a view.
+        preview_samples=k: a float plane between the passes of render_aov_pass(), after k samples; the image is its preview
+        (mp_untile_preview: sums / k), the plane is left as it is."""
         import torch
 
         if plane.dtype == torch.float32:
-            return self.untile(tile_buf=plane, want_u8=False)[0]
+            return self.untile(tile_buf=plane, want_u8=False, preview_samples=preview_samples)[0]
+        if preview_samples is not None:
+            raise ValueError("only float planes have a preview: \"ids\" is the record of sample 0")
         return self.untile(tile_buf=plane.view(torch.float32), want_u8=False)[0].view(plane.dtype)
 
     def rebalance(self) -> List[int]:
