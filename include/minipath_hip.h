@@ -359,6 +359,9 @@ int mp_trace_rays(mp_ctx *ctx, const mp_scene *scene, const float *d_ox, const f
  *      child boxes rounded outward): the result is exactly (t* < b ? mp_trace_rays' record : miss).  Below that, a box whose
  *      floating-point entry lies beyond the distance of a triangle it holds (grazing rays, walls on box faces) can make the
  *      bounded hit differ from the unbounded one although t* < b -- as the reference's own walk does with any best.t.
+ *      Measured rarity (the oracle's W(b), tests/ray_query_scenes.py): 600 axis-aligned rectangles on lattice planes, rays aimed at
+ *      triangle centroids from around the scene: 66 of 200 000 miss with b = nextafter(t*), and 13 of their 44 100 grazing copies
+ *      (one direction component scaled by 1e-4) that still hit.
  *   5. The wide and the literal device trees give the same result for bounded walks (minipath_amd/csrc/device_tree.cpp).
  * There is no tmin: hits with t >= 0 count (as in the reference's own test); callers offset the origin, as the path extension
  * does (1e-4 along the normal).

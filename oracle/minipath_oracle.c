@@ -1135,7 +1135,9 @@ static inline void op_rec(uint8_t v) {
     if (g_ops && g_ops_n < g_ops_cap) { if (g_links) g_links[g_ops_n] = g_cur_link; g_ops[g_ops_n++] = v; }
 }
 
-static void bvh_intersect_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache *st, mpo_hit *out, mpo_counters *cnt) {
+/* start = the value best.t begins with: FloatType::MAX in the reference (:34-37); a bounded query's b (W(b) of
+ * include/minipath_hip.h "Bounded and occlusion queries") changes that one initialiser and nothing else. */
+static void bvh_intersect_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache *st, mpo_hit *out, mpo_counters *cnt, float start) {
     st->n = 0;
     stack_entry root;
     root.link = b->root;
@@ -1143,7 +1145,7 @@ static void bvh_intersect_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache 
     root.t1 = -INFINITY;
     stack_push(st, &root); /* :28-32 */
 
-    leaf_hit best = {FLT_MAX, 0, 0, {0, 0, 0}, MPO_NO_TRIANGLE}; /* :34-37 */
+    leaf_hit best = {start, 0, 0, {0, 0, 0}, MPO_NO_TRIANGLE}; /* :34-37 */
     if (cnt) cnt->rays++;
 
     while (st->n > 0) { /* :39 */
@@ -1205,7 +1207,7 @@ static void bvh_intersect_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache 
 
     memset(out, 0, sizeof(*out));
     out->prim = best.prim;
-    if (best.prim == MPO_NO_TRIANGLE) { out->hit = 0; out->t = best.t; return; } /* :66-67 */
+    if (best.prim == MPO_NO_TRIANGLE) { out->hit = 0; out->t = FLT_MAX; return; } /* :66-67; best.t == start: the miss record keeps f32::MAX */
     /* :69-94 */
     const mpo_tri_shading *sh = &b->shading[best.prim];
     float n[3], tx[3];
@@ -1234,30 +1236,40 @@ static void bvh_intersect_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache 
  * direction, hence t, unchanged), closest wins with a strict `<` (the first member keeps ties); HitRecord.point = point_at(t)
  * of the WORLD ray; normal / tex / material id are the member's, prim is the triangle index inside the member.  The material
  * table and the sky radiance of the path extension are the container's (this BVH's). */
-static void bvh_intersect_impl(const mpo_bvh *b, const mpo_ray *ray, stack_cache *st, mpo_hit *out, mpo_counters *cnt) {
-    if (b->n_inst == 0) { bvh_intersect_one(b, ray, st, out, cnt); return; }
+/* member k's view of the world ray: origin - translation, then origin and direction through the inverse rotation; returns the
+ * member's rotation (NULL = none) */
+static const float *member_ray(const mpo_bvh *b, uint32_t k, const mpo_ray *ray, mpo_ray *r2) {
+    *r2 = *ray;
+    for (int i = 0; i < 3; i++) r2->o[i] = ray->o[i] - b->inst_t[3 * k + i];
+    const float *q = b->inst_q ? &b->inst_q[4 * k] : NULL;
+    if (q) { /* world = q * local + translation: the ray goes through the inverse rotation; the direction is NOT re-normalised
+              * (t keeps the world ray's scale), inv_direction by Ray::new's rule (geometry/mod.rs:49-53) */
+        const float qc[4] = {-q[0], -q[1], -q[2], q[3]};
+        float v[3] = {r2->o[0], r2->o[1], r2->o[2]};
+        quat_rotate(qc, v, r2->o);
+        quat_rotate(qc, ray->d, r2->d);
+        for (int i = 0; i < 3; i++) r2->inv[i] = (r2->d[i] == 0.0f) ? INFINITY : 1.0f / r2->d[i];
+    }
+    return q;
+}
+
+/* start: every member is walked with best.t = start, a Sphere member hits only with t < start; the members combine as before */
+static void bvh_intersect_impl(const mpo_bvh *b, const mpo_ray *ray, stack_cache *st, mpo_hit *out, mpo_counters *cnt, float start) {
+    if (b->n_inst == 0) { bvh_intersect_one(b, ray, st, out, cnt, start); return; }
     mpo_hit best;
     memset(&best, 0, sizeof(best));
     best.prim = MPO_NO_TRIANGLE;
     best.t = FLT_MAX;
     for (uint32_t k = 0; k < b->n_inst; k++) {
-        mpo_ray r2 = *ray;
-        for (int i = 0; i < 3; i++) r2.o[i] = ray->o[i] - b->inst_t[3 * k + i];
-        const float *q = b->inst_q ? &b->inst_q[4 * k] : NULL;
-        if (q) { /* world = q * local + translation: the ray goes through the inverse rotation; the direction is NOT re-normalised
-                  * (t keeps the world ray's scale), inv_direction by Ray::new's rule (geometry/mod.rs:49-53) */
-            const float qc[4] = {-q[0], -q[1], -q[2], q[3]};
-            float v[3] = {r2.o[0], r2.o[1], r2.o[2]};
-            quat_rotate(qc, v, r2.o);
-            quat_rotate(qc, ray->d, r2.d);
-            for (int i = 0; i < 3; i++) r2.inv[i] = (r2.d[i] == 0.0f) ? INFINITY : 1.0f / r2.d[i];
-        }
+        mpo_ray r2;
+        const float *q = member_ray(b, k, ray, &r2);
         mpo_hit h;
         if (b->inst_sph && b->inst_sph[4 * k + 3] >= 0.0f) { /* a Sphere member (primitives.rs:16-48): material 0, tex = origin */
             mpo_sphere_intersect(&b->inst_sph[4 * k], b->inst_sph[4 * k + 3], &r2, &h);
+            if (h.hit && !(h.t < start)) h.hit = 0;
             if (cnt) cnt->rays++;
         } else
-            bvh_intersect_one(b->inst_obj ? b->inst_obj[k] : b, &r2, st, &h, cnt);
+            bvh_intersect_one(b->inst_obj ? b->inst_obj[k] : b, &r2, st, &h, cnt, start);
         if (cnt) cnt->rays--; /* one Object::intersect call of the scene's object, however many members it holds */
         if (h.hit && h.t < best.t) {
             best = h;
@@ -1322,7 +1334,7 @@ size_t mpo_bvh_intersect_ops(const mpo_bvh *b, const mpo_ray *ray, uint8_t *ops,
     stack_cache st = {0};
     mpo_hit h;
     g_ops = ops; g_links = links; g_ops_cap = cap; g_ops_n = 0;
-    bvh_intersect_one(b, ray, &st, &h, NULL);
+    bvh_intersect_one(b, ray, &st, &h, NULL, FLT_MAX);
     size_t n = g_ops_n;
     g_ops = NULL; g_links = NULL; g_ops_cap = 0; g_ops_n = 0;
     free(st.e);
@@ -1331,7 +1343,7 @@ size_t mpo_bvh_intersect_ops(const mpo_bvh *b, const mpo_ray *ray, uint8_t *ops,
 
 void mpo_bvh_intersect(const mpo_bvh *b, const mpo_ray *ray, mpo_hit *out, mpo_counters *cnt) {
     stack_cache st = {0};
-    bvh_intersect_impl(b, ray, &st, out, cnt);
+    bvh_intersect_impl(b, ray, &st, out, cnt, FLT_MAX);
     free(st.e);
 }
 
@@ -1353,7 +1365,7 @@ void mpo_trace_rays(const mpo_bvh *b, const float *ox, const float *oy, const fl
         mpo_ray r;
         mpo_ray_new(o, d, &r);
         mpo_hit h;
-        bvh_intersect_impl(b, &r, &st, &h, cnt);
+        bvh_intersect_impl(b, &r, &st, &h, cnt, FLT_MAX);
         t[i] = h.t;
         prim[i] = h.hit ? (uint32_t)h.prim : 0xFFFFFFFFu;
         u[i] = h.u; v[i] = h.v;
@@ -1373,7 +1385,7 @@ static void render_sample_impl(const mpo_bvh *b, const mpo_sampler *s, uint32_t 
     mpo_ray ray;
     mpo_sample_ray(s, x, y, &rng, &ray); /* :57 */
     mpo_hit h;
-    bvh_intersect_impl(b, &ray, st, &h, cnt); /* :59 */
+    bvh_intersect_impl(b, &ray, st, &h, cnt, FLT_MAX); /* :59 */
     if (h.hit) {
         float d = fabsf(ray.d[0] * h.normal[0] + ray.d[1] * h.normal[1] + ray.d[2] * h.normal[2]); /* :60 */
         rgba[0] = rgba[1] = rgba[2] = d; rgba[3] = 1.0f;
@@ -1403,6 +1415,156 @@ void mpo_sphere_intersect(const float center[3], float radius, const mpo_ray *ra
     mpo_ray_point_at(ray, t, out->point);                                                /* :37 */
     float n[3] = {out->point[0] - center[0], out->point[1] - center[1], out->point[2] - center[2]};
     normalize3(n, out->normal);                                                          /* :38 */
+}
+
+/* ---- bounded closest hit and occlusion (include/minipath_hip.h "Bounded and occlusion queries"; build-defined) ---------- */
+/* effective bound b = min(tmax, f32::MAX), NULL = f32::MAX; 0 = NaN or tmax <= 0: a miss that is not walked */
+static inline float query_bound(const float *tmax, uint64_t i) {
+    const float tm = tmax ? tmax[i] : FLT_MAX;
+    return tm > 0.0f ? fast_min(tm, FLT_MAX) : 0.0f;
+}
+
+static void store_hit(const mpo_hit *h, uint64_t i, float *t, uint32_t *prim, float *u, float *v, float *point, float *normal,
+                      float *tex, uint32_t *material, uint32_t *instance) {
+    if (t) t[i] = h->hit ? h->t : FLT_MAX;
+    if (prim) prim[i] = h->hit ? (uint32_t)h->prim : 0xFFFFFFFFu;
+    if (u) u[i] = h->hit ? h->u : 0.0f;
+    if (v) v[i] = h->hit ? h->v : 0.0f;
+    for (int k = 0; k < 3; k++) {
+        if (point) point[3 * i + k] = h->hit ? h->point[k] : 0.0f;
+        if (normal) normal[3 * i + k] = h->hit ? h->normal[k] : 0.0f;
+        if (tex) tex[3 * i + k] = h->hit ? h->tex[k] : 0.0f;
+    }
+    if (material) material[i] = h->hit ? (uint32_t)h->material : 0u;
+    if (instance) instance[i] = h->hit ? h->instance : 0u;
+}
+
+void mpo_trace_rays_bounded(const mpo_bvh *b, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,
+                            const float *dz, const float *tmax, uint64_t n, float *t, uint32_t *prim, float *u, float *v,
+                            float *point, float *normal, float *tex, uint32_t *material, uint32_t *instance) {
+    stack_cache st = {0};
+    for (uint64_t i = 0; i < n; i++) {
+        mpo_hit h;
+        memset(&h, 0, sizeof(h));
+        const float bound = query_bound(tmax, i);
+        if (bound > 0.0f) {
+            float o[3] = {ox[i], oy[i], oz[i]}, d[3] = {dx[i], dy[i], dz[i]};
+            mpo_ray r;
+            mpo_ray_new(o, d, &r);
+            bvh_intersect_impl(b, &r, &st, &h, NULL, bound);
+        }
+        store_hit(&h, i, t, prim, u, v, point, normal, tex, material, instance);
+    }
+    free(st.e);
+}
+
+void mpo_sphere_trace_bounded(const float center[3], float radius, const float *ox, const float *oy, const float *oz,
+                              const float *dx, const float *dy, const float *dz, const float *tmax, uint64_t n, float *t,
+                              uint32_t *prim, float *u, float *v, float *point, float *normal, float *tex, uint32_t *material,
+                              uint32_t *instance) {
+    for (uint64_t i = 0; i < n; i++) {
+        mpo_hit h;
+        memset(&h, 0, sizeof(h));
+        const float bound = query_bound(tmax, i);
+        if (bound > 0.0f) {
+            float o[3] = {ox[i], oy[i], oz[i]}, d[3] = {dx[i], dy[i], dz[i]};
+            mpo_ray r;
+            mpo_ray_new(o, d, &r);
+            mpo_sphere_intersect(center, radius, &r, &h);
+            if (h.hit && !(h.t < bound)) h.hit = 0; /* a hit counts below b */
+        }
+        store_hit(&h, i, t, prim, u, v, point, normal, tex, material, instance);
+    }
+}
+
+/* The any-hit walk, written on its own (NOT "bounded prim != NO_PRIM": the tests compare the two): ray_bvh_intersection.rs:26-62
+ * with best.t = bound, which never changes because the walk ends at the first packet holding a triangle that passes the leaf
+ * test (:125) with t < bound. */
+static int bvh_occluded_one(const mpo_bvh *b, const mpo_ray *ray, stack_cache *st, float bound) {
+    st->n = 0;
+    stack_entry root;
+    root.link = b->root;
+    for (int k = 0; k < 3; k++) { root.mn[k] = b->bbox_min[k]; root.size[k] = b->bbox_max[k] - b->bbox_min[k]; }
+    root.t1 = -INFINITY;
+    stack_push(st, &root);
+    while (st->n > 0) {
+        stack_entry e = st->e[--st->n];
+        if (e.t1 > bound) continue; /* :40-44 */
+        uint32_t index, count;
+        int kind = mpo_link_decode(e.link, &index, &count);
+        if (kind == 0) continue;
+        if (kind == 1) {
+            const mpo_inner_node *node = &b->inner[index];
+            float bmin[3][8], bmax[3][8], t1[8], t2[8];
+            for (int k = 0; k < 3; k++) {
+                decompress8(node->bmin[k], e.size[k], e.mn[k], bmin[k]);
+                decompress8(node->bmax[k], e.size[k], e.mn[k], bmax[k]);
+            }
+            mpo_aabb8_intersect(bmin, bmax, ray, bound, t1, t2);
+            for (int i = 0; i < L8; i++) {
+                if (!(t1[i] <= t2[i])) continue;
+                stack_entry c;
+                c.link = node->link[i];
+                for (int k = 0; k < 3; k++) { c.mn[k] = bmin[k][i]; c.size[k] = bmax[k][i] - bmin[k][i]; }
+                c.t1 = t1[i];
+                stack_push(st, &c);
+            }
+            continue;
+        }
+        for (uint32_t j = index; j < index + count; j++) {
+            const mpo_tri_packet *pk = &b->packets[j];
+            float v[3][3][8], t[8], u[8], vv[8];
+            for (int a = 0; a < 3; a++)
+                for (int k = 0; k < 3; k++) decompress8(pk->v[a][k], e.size[k], e.mn[k], v[a][k]);
+            unsigned mask = mpo_tri8_intersect(v[0], v[1], v[2], ray, t, u, vv);
+            for (int i = 0; i < L8; i++)
+                if (((mask >> i) & 1u) && t[i] >= 0.0f && t[i] <= bound && t[i] < bound) return 1;
+        }
+    }
+    return 0;
+}
+
+static int sphere_occluded(const float center[3], float radius, const mpo_ray *ray, float bound) {
+    mpo_hit h;
+    mpo_sphere_intersect(center, radius, ray, &h);
+    return h.hit && h.t < bound;
+}
+
+void mpo_occluded_rays(const mpo_bvh *b, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,
+                       const float *dz, const float *tmax, uint64_t n, uint8_t *occluded) {
+    stack_cache st = {0};
+    for (uint64_t i = 0; i < n; i++) {
+        occluded[i] = 0;
+        const float bound = query_bound(tmax, i);
+        if (!(bound > 0.0f)) continue;
+        float o[3] = {ox[i], oy[i], oz[i]}, d[3] = {dx[i], dy[i], dz[i]};
+        mpo_ray r;
+        mpo_ray_new(o, d, &r);
+        if (b->n_inst == 0) { occluded[i] = (uint8_t)bvh_occluded_one(b, &r, &st, bound); continue; }
+        for (uint32_t k = 0; k < b->n_inst && !occluded[i]; k++) { /* the first member that reports a hit ends the query */
+            mpo_ray r2;
+            member_ray(b, k, &r, &r2);
+            if (b->inst_sph && b->inst_sph[4 * k + 3] >= 0.0f)
+                occluded[i] = (uint8_t)sphere_occluded(&b->inst_sph[4 * k], b->inst_sph[4 * k + 3], &r2, bound);
+            else
+                occluded[i] = (uint8_t)bvh_occluded_one(b->inst_obj ? b->inst_obj[k] : b, &r2, &st, bound);
+        }
+    }
+    free(st.e);
+}
+
+void mpo_sphere_occluded_rays(const float center[3], float radius, const float *ox, const float *oy, const float *oz,
+                              const float *dx, const float *dy, const float *dz, const float *tmax, uint64_t n,
+                              uint8_t *occluded) {
+    for (uint64_t i = 0; i < n; i++) {
+        occluded[i] = 0;
+        const float bound = query_bound(tmax, i);
+        if (!(bound > 0.0f)) continue;
+        float o[3] = {ox[i], oy[i], oz[i]}, d[3] = {dx[i], dy[i], dz[i]};
+        mpo_ray r;
+        mpo_ray_new(o, d, &r);
+        occluded[i] = (uint8_t)sphere_occluded(center, radius, &r, bound);
+    }
 }
 
 /* render_tile (worker.rs:32-49) over Scene<Sphere> */
@@ -1464,7 +1626,7 @@ static void render_sample_paths_impl(const mpo_bvh *b, const mpo_sampler *s, uin
     float L[3] = {0.0f, 0.0f, 0.0f}, thr[3] = {1.0f, 1.0f, 1.0f}, alpha = 0.0f;
     for (uint32_t depth = 1; depth <= max_depth; depth++) {
         mpo_hit h;
-        bvh_intersect_impl(b, &ray, st, &h, cnt);
+        bvh_intersect_impl(b, &ray, st, &h, cnt, FLT_MAX);
         if (segments) (*segments)++;
         if (!h.hit) { for (int c = 0; c < 3; c++) L[c] = L[c] + thr[c] * b->sky; break; }
         if (depth == 1) alpha = 1.0f;

@@ -221,6 +221,27 @@ void mpo_trace_rays_inst(const mpo_bvh *b, const float *ox, const float *oy, con
                          const float *dy, const float *dz, uint64_t n, float *t, uint32_t *prim, float *u, float *v,
                          uint32_t *inst);
 
+/* ---- bounded closest hit and occlusion: include/minipath_hip.h "Bounded and occlusion queries" (build-defined) --- */
+/* W(b) to the letter: b = min(tmax, f32::MAX), tmax == NULL means f32::MAX; NaN or tmax <= 0 is a miss that is not walked;
+ * otherwise mpo_bvh_intersect with best.t starting at b (groups and instances: every member with best.t = b, a Sphere member
+ * only with t < b, combined as mpo_bvh_intersect combines).  Every output is nullable and is one mp_hits_soa field: t, prim, u,
+ * v, material, instance n entries, point / normal / tex n*3.  A miss writes t = f32::MAX, prim = 0xFFFFFFFF and zeros. */
+void mpo_trace_rays_bounded(const mpo_bvh *b, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,
+                            const float *dz, const float *tmax /* nullable */, uint64_t n, float *t, uint32_t *prim, float *u,
+                            float *v, float *point, float *normal, float *tex, uint32_t *material, uint32_t *instance);
+/* The any-hit walk, a walk of its own: it stops at the first packet in which a triangle passes the leaf test with t < b, a
+ * group at the first member that reports one.  occluded: n bytes, 1 / 0. */
+void mpo_occluded_rays(const mpo_bvh *b, const float *ox, const float *oy, const float *oz, const float *dx, const float *dy,
+                       const float *dz, const float *tmax /* nullable */, uint64_t n, uint8_t *occluded);
+/* the same two for a plain Sphere scene (scene/primitives.rs:16-48: t, and a hit only with t < b) */
+void mpo_sphere_trace_bounded(const float center[3], float radius, const float *ox, const float *oy, const float *oz,
+                              const float *dx, const float *dy, const float *dz, const float *tmax, uint64_t n, float *t,
+                              uint32_t *prim, float *u, float *v, float *point, float *normal, float *tex, uint32_t *material,
+                              uint32_t *instance);
+void mpo_sphere_occluded_rays(const float center[3], float radius, const float *ox, const float *oy, const float *oz,
+                              const float *dx, const float *dy, const float *dz, const float *tmax, uint64_t n,
+                              uint8_t *occluded);
+
 /* ---- renderer/worker.rs --------------------------------------------------------------------------- */
 /* render_sample :51-66 with the build-defined seeded RNG: returns rgba */
 void mpo_render_sample(const mpo_bvh *b, const mpo_sampler *s, uint32_t width, uint32_t spp, uint64_t seed,

@@ -164,6 +164,12 @@ def lib() -> C.CDLL:
     L.mpo_bvh_set_group_rotations.argtypes = [C.c_void_p, f32p]
     L.mpo_bvh_set_group_rotations.restype = C.c_int
     L.mpo_trace_rays_inst.argtypes = [C.c_void_p] + [f32p] * 6 + [C.c_uint64, f32p, u32p, f32p, f32p, u32p]
+    u8p = C.POINTER(C.c_uint8)
+    soa = [f32p, u32p, f32p, f32p, f32p, f32p, f32p, u32p, u32p]  # t, prim, u, v, point, normal, tex, material, instance
+    L.mpo_trace_rays_bounded.argtypes = [C.c_void_p] + [f32p] * 7 + [C.c_uint64] + soa
+    L.mpo_occluded_rays.argtypes = [C.c_void_p] + [f32p] * 7 + [C.c_uint64, u8p]
+    L.mpo_sphere_trace_bounded.argtypes = [f32p, C.c_float] + [f32p] * 7 + [C.c_uint64] + soa
+    L.mpo_sphere_occluded_rays.argtypes = [f32p, C.c_float] + [f32p] * 7 + [C.c_uint64, u8p]
     L.mpo_seed_mix.argtypes = [C.c_uint64]
     L.mpo_seed_mix.restype = C.c_uint64
     L.mpo_bvh_free.argtypes = [C.c_void_p]
@@ -247,6 +253,25 @@ def _u32p(a: np.ndarray):
 
 def vec3(x, y, z):
     return (C.c_float * 3)(x, y, z)
+
+
+FULL = ("t", "prim", "u", "v", "point", "normal", "tex", "material", "instance")  # the fields of mp_hits_soa
+
+
+def _query_args(o, d, tmax):
+    """SoA ray columns and the bound array (None = NULL) of a bounded query"""
+    o = np.ascontiguousarray(o, np.float32)
+    d = np.ascontiguousarray(d, np.float32)
+    n = o.shape[0]
+    cols = [np.ascontiguousarray(o[:, k]) for k in range(3)] + [np.ascontiguousarray(d[:, k]) for k in range(3)]
+    tm = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+    return cols, tm, n
+
+
+def _hits_soa(n):
+    out = {k: np.zeros((n, 3) if k in ("point", "normal", "tex") else n, np.uint32 if k in ("prim", "material", "instance") else np.float32)
+           for k in FULL}
+    return out, [(_u32p if out[k].dtype == np.uint32 else _f32p)(out[k]) for k in FULL]
 
 
 def ray_new(o, d) -> Ray:
@@ -397,6 +422,22 @@ class Bvh:
         lib().mpo_trace_rays_inst(self.h, *[_f32p(c) for c in cols], n, _f32p(t), _u32p(prim), _f32p(u), _f32p(v), _u32p(inst))
         return t, prim, u, v, inst
 
+    def trace_bounded(self, o: np.ndarray, d: np.ndarray, tmax=None) -> dict:
+        """mpo_trace_rays_bounded: W(b) of include/minipath_hip.h for every ray.  tmax: None (NULL: f32::MAX), a scalar or float32
+        [n].  Returns every mp_hits_soa field (FULL) as arrays; prim / material / instance are uint32."""
+        cols, tm, n = _query_args(o, d, tmax)
+        out, ptrs = _hits_soa(n)
+        lib().mpo_trace_rays_bounded(self.h, *[_f32p(c) for c in cols], None if tm is None else _f32p(tm), n, *ptrs)
+        return out
+
+    def occluded(self, o: np.ndarray, d: np.ndarray, tmax=None) -> np.ndarray:
+        """mpo_occluded_rays: the early-exit walk of its own; bool [n]."""
+        cols, tm, n = _query_args(o, d, tmax)
+        occ = np.zeros(n, np.uint8)
+        lib().mpo_occluded_rays(self.h, *[_f32p(c) for c in cols], None if tm is None else _f32p(tm), n,
+                                occ.ctypes.data_as(C.POINTER(C.c_uint8)))
+        return occ.astype(bool)
+
     def tri_material(self) -> np.ndarray:
         return self._view(lib().mpo_bvh_tri_material(self.h), self.n_packets * 8 * 4, np.uint32).copy()
 
@@ -530,6 +571,23 @@ def sphere_intersect(center, radius, ray: Ray) -> Hit:
     h = Hit()
     lib().mpo_sphere_intersect(vec3(*center), C.c_float(radius), C.byref(ray), C.byref(h))
     return h
+
+
+def sphere_trace_bounded(center, radius, o, d, tmax=None) -> dict:
+    """Bvh.trace_bounded for a plain Sphere scene (mpo_sphere_trace_bounded)."""
+    cols, tm, n = _query_args(o, d, tmax)
+    out, ptrs = _hits_soa(n)
+    lib().mpo_sphere_trace_bounded(vec3(*center), C.c_float(radius), *[_f32p(c) for c in cols], None if tm is None else _f32p(tm), n, *ptrs)
+    return out
+
+
+def sphere_occluded(center, radius, o, d, tmax=None) -> np.ndarray:
+    """Bvh.occluded for a plain Sphere scene (mpo_sphere_occluded_rays)."""
+    cols, tm, n = _query_args(o, d, tmax)
+    occ = np.zeros(n, np.uint8)
+    lib().mpo_sphere_occluded_rays(vec3(*center), C.c_float(radius), *[_f32p(c) for c in cols], None if tm is None else _f32p(tm), n,
+                                   occ.ctypes.data_as(C.POINTER(C.c_uint8)))
+    return occ.astype(bool)
 
 
 def render_tile_sphere(center, radius, sampler: Sampler, width, spp, seed, x0, y0, x1, y1):

@@ -39,7 +39,30 @@ def _sphere(n):
     return pos, nrm, tex, tri
 
 
+def _walls(n, seed, extent=8.0, snap=0.0):
+    """n axis-aligned rectangles (two triangles each) in a cube of side `extent`: leaf and inner boxes with zero thickness along
+    the rectangle's normal, so triangles lie ON box faces -- where a box's floating-point slab entry can exceed the distance of a
+    triangle it holds (include/minipath_hip.h, consequence 4 of the bounded queries)."""
+    rng = np.random.default_rng(seed)
+    c = (rng.random((n, 3), dtype=np.float32) - 0.5) * np.float32(extent)
+    half = 0.1 + rng.random((n, 2), dtype=np.float32) * 0.9
+    axis = rng.integers(0, 3, n)
+    if snap:  # walls on the planes of a lattice: many of them end up exactly on a face of their node's box
+        c[np.arange(n), axis] = np.round(c[np.arange(n), axis] / np.float32(snap)) * np.float32(snap)
+    corners = np.array([[-1, -1], [1, -1], [1, 1], [-1, 1]], np.float32)
+    pos = np.repeat(c[:, None, :], 4, axis=1)
+    for k in range(n):
+        a, b = [x for x in range(3) if x != axis[k]]
+        pos[k, :, a] += corners[:, 0] * half[k, 0]
+        pos[k, :, b] += corners[:, 1] * half[k, 1]
+    base = (np.arange(n, dtype=np.uint32) * 4)[:, None]
+    tri = np.concatenate([base + np.array([0, 1, 2], np.uint32), base + np.array([0, 2, 3], np.uint32)], axis=1).reshape(-1, 3)
+    return pos.reshape(-1, 3).astype(np.float32), None, None, tri.astype(np.uint32)
+
+
 def make(name):
+    if name == "walls_600":
+        return _walls(600, 17, snap=2.0)
     if name == "soup_300":
         return _soup(300, 11)
     if name == "soup_5000":

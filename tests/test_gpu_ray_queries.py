@@ -1,6 +1,9 @@
 """GPU tests of the bounded closest-hit and occlusion queries (mp_trace_rays_bounded / mp_occluded_rays; definitions and facts in
-include/minipath_hip.h "Bounded and occlusion queries").  The oracle has no bounded walk: everything is derived from its unbounded
-trace (t* = the unbounded closest-hit distance) through the facts, and from the GPU's own unbounded mp_trace_rays.
+include/minipath_hip.h "Bounded and occlusion queries").  The kernels are compared bit for bit, in every mp_hits_soa field, with the
+oracle's W(b) (mpo_trace_rays_bounded) and with its early-exit walk (mpo_occluded_rays), which tests/test_ray_queries_oracle_cpu.py
+pins on the CPU -- on random and camera rays, on the band rays of the wall scene, on secondary rays started on surfaces, and on
+launches whose grid-stride loop takes more than two steps.  Beside that the facts stay asserted as they were, from the oracle's
+unbounded trace (t* = the unbounded closest-hit distance) and the GPU's own unbounded mp_trace_rays:
   1. tmax NULL / +inf / f32::MAX: the bits of mp_trace_rays in every field;
   2. t* >= b or an unbounded miss: a miss (and NaN / tmax <= 0: a miss);
   3. a bounded hit at t: t* <= t < b (the header's exception, a ray crossing two boxes whose floating-point entry lies past a
@@ -13,21 +16,16 @@ import numpy as np
 import pytest
 
 import minipath_amd as mp
-from minipath_amd import _lib, scenes
-from tests import meshes
+from minipath_amd import _lib
+from tests import dispatch_cases as dc
+from tests import plan_probe as pp
+from tests import ray_query_scenes as rq
 from tests.conftest import TEAPOT
+from tests.ray_query_scenes import FMAX, FULL, NO, F, bits
 
 pytestmark = pytest.mark.gpu
 
-F = np.float32
-FMAX = np.finfo(F).max
-NO = 0xFFFFFFFF
-MESHES = ["soup_300", "soup_5000", "grid_40", "sphere_24", "flat_plane", "two_clusters", "sliver_fan"]
-SCENES = ["teapot", "atrium"] + MESHES + ["sphere", "group", "instances"]
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+MESHES, SCENES = rq.MESHES, rq.SCENES
 
 
 @pytest.fixture(scope="module")
@@ -38,81 +36,11 @@ def ctx():
     return mp.Context(0)
 
 
-def _quats(rng, n):
-    q = rng.standard_normal((n, 4)).astype(F)
-    q /= np.sqrt((q.astype(np.float64) ** 2).sum(axis=1, keepdims=True)).astype(F)
-    q[0] = (0.0, 0.0, 0.0, 1.0)
-    return q.astype(F)
-
-
-def _camera_rays(oracle, n, seed):
-    s = oracle.build_sampler(oracle.teapot_camera(), 256, 256)
-    rng = np.random.default_rng(seed)
-    o, d = np.zeros((n, 3), F), np.zeros((n, 3), F)
-    for i in range(n):
-        r = oracle.sample_ray(s, int(rng.integers(0, 256)), int(rng.integers(0, 256)), 77 + i)
-        o[i], d[i] = list(r.o), list(r.d)
-    return o, d
-
-
 def _make(name, ctx, oracle):
-    """(GPU scene object, oracle trace (o, d) -> t, prim, u, v, inst, rays o, d)"""
-    if name == "teapot":
-        gpu, orc = mp.TriangleBvh.with_obj(TEAPOT, ctx), oracle.Bvh.from_obj(TEAPOT)
-        o1, d1 = meshes.random_rays(12000, 31, *orc.bbox())
-        o2, d2 = _camera_rays(oracle, 4000, 5)
-        o, d = np.concatenate([o1, o2]), np.concatenate([d1, d2])
-        return gpu, (lambda o, d: (*orc.trace(o, d), np.zeros(o.shape[0], np.uint32))), o, d
-    if name == "atrium" or name in MESHES:
-        pos, nrm, tex, tri = scenes.atrium(1, 0.05) if name == "atrium" else meshes.make(name)
-        gpu, orc = mp.TriangleBvh.build(pos, nrm, tex, tri, ctx), oracle.Bvh.build(pos, nrm, tex, tri)
-        bmin, bmax = orc.bbox()
-        o, d = meshes.random_rays(16000, 41, bmin, np.maximum(bmax, bmin + 1e-3))
-        # and rays aimed at triangle centroids: hits on sparse scenes too
-        rng = np.random.default_rng(42)
-        c = pos[tri[rng.integers(0, tri.shape[0], 4000)]].mean(axis=1).astype(F)
-        d[-4000:] = (c - o[-4000:]).astype(F)
-        return gpu, (lambda o, d: (*orc.trace(o, d), np.zeros(o.shape[0], np.uint32))), o, d
-    if name == "sphere":
-        c, r = (1.0, 2.0, 3.0), 1.5
-        gpu = mp.Sphere(c, r, ctx)
-        o, d = meshes.random_rays(3000, 43, np.array(c, F) - r, np.array(c, F) + r)
-
-        def trace(o, d):
-            n = o.shape[0]
-            t, prim = np.full(n, FMAX, F), np.full(n, NO, np.uint32)
-            for i in range(n):
-                h = oracle.sphere_intersect(c, r, oracle.ray_new(o[i], d[i]))
-                if h.hit:
-                    t[i], prim[i] = h.t, 0
-            return t, prim, np.zeros(n, F), np.zeros(n, F), np.zeros(n, np.uint32)
-
-        return gpu, trace, o, d
-    if name == "group":
-        rng = np.random.default_rng(19)
-        pos, nrm, tex, tri = meshes.make("soup_300")
-        teapot, soup, ball = mp.TriangleBvh.with_obj(TEAPOT, ctx), mp.TriangleBvh.build(pos, nrm, tex, tri, ctx), mp.Sphere((0.4, 0, 0), 1.0, ctx)
-        o_teapot, o_soup = oracle.Bvh.from_obj(TEAPOT), oracle.Bvh.build(pos, nrm, tex, tri)
-        tr = np.array([[0, 0, 0], [7.0, 0.5, -2.0], [-5.5, 2.0, 1.0], [0.0, 5.0, -1.0], [3.0, 4.5, 2.5]], F)
-        q = _quats(rng, 5)
-        gpu = mp.ObjectGroup([teapot, teapot, soup, ball, soup], tr, rotations=q)
-        box = oracle.Bvh.from_obj(TEAPOT)
-        box.set_group([box, o_teapot, o_soup, ((0.4, 0.0, 0.0), 1.0), o_soup], tr, rotations=q)
-        gpu._keep = (teapot, soup, ball, box, o_teapot, o_soup)
-        i = gpu.info()
-        o, d = meshes.random_rays(16000, 23, np.array(list(i.bbox_min), F), np.array(list(i.bbox_max), F))
-        return gpu, box.trace_inst, o, d
-    if name == "instances":
-        base = mp.TriangleBvh.with_obj(TEAPOT, ctx)
-        tr = np.array([[0, 0, 0], [7.5, 0, -3], [-7.0, 0.5, -6], [0.25, 3.4, -1.0]], F)
-        gpu = mp.Instances(base, tr)
-        orc = oracle.Bvh.from_obj(TEAPOT)
-        orc.set_instances(tr)
-        gpu._keep = (orc,)
-        i = gpu.info()
-        o, d = meshes.random_rays(16000, 4, np.array(list(i.bbox_min), F), np.array(list(i.bbox_max), F))
-        return gpu, orc.trace_inst, o, d
-    raise KeyError(name)
+    """(GPU scene object, oracle trace (o, d) -> t, prim, u, v, inst, rays o, d); the scenes are tests/ray_query_scenes.py's"""
+    gpu, orc, o, d = rq.make(name, ctx, oracle)
+    gpu._oracle = orc
+    return gpu, orc.trace, o, d
 
 
 def _cuda(*a):
@@ -139,9 +67,6 @@ def _box_exit(scene, o, d):
     far = np.where(np.isnan(np.maximum(a, c)), np.inf, np.maximum(a, c)).min(axis=1)
     far = np.where(np.isfinite(far), far, 0.0)
     return (np.maximum(far, 0.0) * (1 + 1e-3) + 1e-2 * (1 + np.abs(hi - lo).max())).astype(F)
-
-
-FULL = ("t", "prim", "u", "v", "point", "normal", "tex", "material", "instance")
 
 
 @pytest.mark.parametrize("name", SCENES)
@@ -173,7 +98,7 @@ def test_unbounded_bound_gives_the_same_bits(ctx, oracle, name):
 
 def _tmax_rounds(ts, hit, exit_, rng):
     """per-ray bounds: around t* for hits ({t*(1-2^-8), t*, nextafter(t*), t*(1+2^-8), 2 t*}), finite values for misses, then 0 /
-    -1 / NaN / positive denormals mixed in, then the fact-4 level"""
+    -1 / NaN / positive denormals mixed in, then the fact-4 level, then t* + 2 and + 4 ulp"""
     n = ts.shape[0]
     tsf = np.where(hit, ts, F(1)).astype(F)
     around = [tsf * F(1 - 2**-8), tsf, np.nextafter(tsf, F(np.inf)), tsf * F(1 + 2**-8), tsf * F(2)]
@@ -186,12 +111,43 @@ def _tmax_rounds(ts, hit, exit_, rng):
     rounds.append(mixed)
     rounds.append(exit_)
     rounds.append(exit_ * F(4))
+    for ulps in (2, 4):
+        rounds.append(np.where(hit, _ulps_up(tsf, ulps), miss_vals).astype(F))
     return rounds
+
+
+def _ulps_up(x, k):
+    for _ in range(k):
+        x = np.nextafter(x, F(np.inf))
+    return x
+
+
+def _obj(scene):
+    """the OBJ template argument of the scene's ray kernels"""
+    return "true" if isinstance(scene, (mp.ObjectGroup, mp.Instances)) else "false"
+
+
+def _assert_exact(ctx, scene, orc, o, d, tm, to=None, td=None):
+    """Both queries against the oracle's walks, bit for bit in every field, and the kernels that ran.  Returns (records, occluded)."""
+    if to is None:
+        to, td = _cuda(o, d)
+    (tt,) = _cuda(tm)
+    want, wocc = orc.trace_bounded(o, d, tm), orc.occluded(o, d, tm)
+    got = _host(scene.intersect(to, td, full=True, tmax=tt))
+    assert ctx.last_kernels() == [f"query_rays_kernel<{_obj(scene)}, kBounded>"]
+    occ = scene.occluded(to, td, tmax=tt).cpu().numpy()
+    assert ctx.last_kernels() == [f"query_rays_kernel<{_obj(scene)}, kAnyHit>"]
+    for k in FULL:
+        bad = (bits(got[k]) != bits(want[k])).reshape(o.shape[0], -1).any(axis=1)
+        assert not bad.any(), f"{k}: {int(bad.sum())} rays, first {int(np.flatnonzero(bad)[0])}"
+    assert np.array_equal(occ, wocc), f"{int((occ != wocc).sum())} rays"
+    return got, occ
 
 
 @pytest.mark.parametrize("name", SCENES)
 def test_bounded_and_occluded_against_the_oracle(ctx, oracle, name):
-    """Facts 2, 3 and 4 against the oracle's unbounded trace, and occluded == bounded hit, on every bound."""
+    """Every field of the bounded query and the occlusion query against the oracle's W(b) and early-exit walk, bit for bit, on
+    every bound; beside them facts 2, 3 and 4 against the oracle's unbounded trace, and occluded == bounded hit."""
     scene, trace, o, d = _make(name, ctx, oracle)
     ts, prim, u, v, inst = trace(o, d)
     hit = prim != NO
@@ -203,9 +159,7 @@ def test_bounded_and_occluded_against_the_oracle(ctx, oracle, name):
     rng = np.random.default_rng(3)
     n4 = nb = 0
     for tm in _tmax_rounds(ts, hit, exit_, rng):
-        (tt,) = _cuda(tm)
-        got = _host(scene.intersect(to, td, full=True, tmax=tt))
-        occ = scene.occluded(to, td, tmax=tt).cpu().numpy()
+        got, occ = _assert_exact(ctx, scene, scene._oracle, o, d, tm, to, td)
         gp = got["prim"].view(np.uint32)
         ghit = gp != NO
         b = np.where(tm > 0, np.minimum(tm, FMAX), F(0))  # NaN compares false: b = 0
@@ -228,6 +182,140 @@ def test_bounded_and_occluded_against_the_oracle(ctx, oracle, name):
         assert not ghit[f4 & ~keep].any()
         n4 += int(keep.sum())
     assert nb > 0 and (n4 > 100 or name == "flat_plane")
+
+
+def _mixed_bounds(ts, hit, rng):
+    """one bound per ray: around t* for hits ({t*(1-2^-8), t*, t* + 1, 2 and 4 ulp, t*(1+2^-8), 2 t*}), finite values for misses,
+    and the values that are not walked (0, -0, -1, NaN, -inf) and positive denormals on three rays in ten"""
+    n = ts.shape[0]
+    tsf = np.where(hit, ts, F(1)).astype(F)
+    around = [tsf * F(1 - 2**-8), tsf, _ulps_up(tsf, 1), _ulps_up(tsf, 2), _ulps_up(tsf, 4), tsf * F(1 + 2**-8), tsf * F(2)]
+    tm = np.where(hit, np.stack(around)[rng.integers(0, len(around), n), np.arange(n)], np.exp(rng.uniform(-3, 9, n))).astype(F)
+    special = np.array([0.0, -1.0, np.nan, np.float32(1e-45), np.float32(3e-39), -0.0, -np.inf], F)
+    pick = rng.random(n) < 0.3
+    tm[pick] = special[rng.integers(0, special.shape[0], int(pick.sum()))]
+    return tm
+
+
+@pytest.mark.parametrize("name", ["walls", "wall_group"])
+def test_band_rays(ctx, oracle, name):
+    """The band fixture (tests/ray_query_scenes.py; 79 band rays, tests/test_ray_queries_oracle_cpu.py::test_band_fixture): rays
+    on which W(nextafter(t*)) is not what the facts derive from the unbounded trace, among 4 000 ordinary rays of the wall scene,
+    through both queries -- the scene on its own and as a member of a two-member rotated group.  Bit-equal to the oracle at
+    t* + 0, 1, 2 and 4 ulp, t*(1 +- 2^-8), 2 t* and a mixed round with the special values."""
+    scene, _, o, d = _make(name, ctx, oracle)
+    orc = scene._oracle
+    band, unb, _ = rq.band_mask(orc, o, d)
+    assert band.sum() >= 32, int(band.sum())
+    hit = unb["prim"] != NO
+    ts = np.where(hit, unb["t"], F(1)).astype(F)
+    to, td = _cuda(o, d)
+    got, occ = _assert_exact(ctx, scene, orc, o, d, _ulps_up(ts, 1), to, td)
+    # what makes them band rays, seen on the GPU: not the unbounded record although t* < b
+    differs = np.zeros(o.shape[0], bool)
+    for k in FULL:
+        differs |= (bits(got[k]) != bits(unb[k])).reshape(o.shape[0], -1).any(axis=1)
+    assert np.array_equal(differs & hit, band)
+    rounds = [ts, _ulps_up(ts, 2), _ulps_up(ts, 4), ts * F(1 - 2**-8), ts * F(1 + 2**-8), ts * F(2), np.full(o.shape[0], FMAX, F),
+              _mixed_bounds(unb["t"], hit, np.random.default_rng(8))]
+    for tm in rounds:
+        _assert_exact(ctx, scene, orc, o, d, tm.astype(F), to, td)
+
+
+@pytest.mark.parametrize("name", list(rq.SECONDARY))
+def test_secondary_rays(ctx, oracle, name):
+    """Rays that start ON a surface, as the documented callers send them: from the hit points of about 8 000 primary rays (the
+    oracle's records), offset 1e-4 along the normal towards the incoming ray -- inside many nested boxes with slab entry 0.
+    Shadow rays to a point light (un-normalised, tmax = dist (1 - 1e-4)) and random bounce rays (tmax = 2 and 0.05): records and
+    occlusion bit-equal to the oracle; between 5 % and 95 % of every set is occluded, so none is vacuous.
+    Occluded shares (shadow, tmax 2, tmax 0.05): teapot 46 / 53 / 51 %, grid_40 50 / 57 / 51 %, atrium 21 / 57 / 51 %, walls
+    80 / 64 / 50 %, group 67 / 53 / 49 %."""
+    scene, _, o, d = _make(name, ctx, oracle)
+    orc = scene._oracle
+    for key, (so, sd, tm) in rq.secondary_rays(orc, *rq.primary_rays(name, orc, o, d), rq.SECONDARY[name], 5).items():
+        assert so.shape[0] > 1000
+        _, occ = _assert_exact(ctx, scene, orc, so, sd, tm)
+        print(f"{name} {key}: {so.shape[0]} rays, {occ.mean():.3f} occluded")
+        assert 0.05 < occ.mean() < 0.95, (key, occ.mean())
+
+
+BASE = 4099  # shares no factor with 64: every chunk of the tiled set sees another alignment of the base rays
+
+
+@pytest.mark.parametrize("api", ["trace", "bounded", "occluded"])
+@pytest.mark.parametrize("name", ["teapot", "instances"])
+def test_more_than_two_sweeps(ctx, oracle, name, api):
+    """The grid-stride loop of trace_rays_kernel and query_rays_kernel<OBJ, MODE> (OBJ = false: teapot, true: instances) beyond
+    its first step: plan_ray_query caps the grid at cu_count * 8 blocks of 4 waves of 64 rays, and n = 2 * grid * 256 + 4099 + 37
+    rays (1 052 712 with grid 2048 at 256 CUs) make every wave take a second chunk and some a third -- a fresh kernarg view, and
+    the LDS queue and stack of the chunk before.  The rays are 4 099 base rays with oracle records and mixed bounds, tiled on
+    the device: row i of every output is the record of base ray i % 4099."""
+    import torch
+
+    scene, _, o, d = _make(name, ctx, oracle)
+    orc = scene._oracle
+    o, d = np.ascontiguousarray(o[-BASE:]), np.ascontiguousarray(d[-BASE:])
+    unb = orc.trace_bounded(o, d)
+    hit = unb["prim"] != NO
+    assert 0.1 < hit.mean() < 0.9
+    tm = _mixed_bounds(unb["t"], hit, np.random.default_rng(12))
+    want = unb if api == "trace" else orc.trace_bounded(o, d, tm)
+    wocc = orc.occluded(o, d, tm)
+    assert 0.05 < wocc.mean() < 0.95 and np.isnan(tm).any() and (tm == 0).any()
+    # the launch: the grid the plan gives for n rays, and n more than two sweeps of it
+    facts = {**dc.scene_facts("teapot"), "stack_bound": scene.info().stack_bound, "members": 4 if name == "instances" else 0}
+    kind = {"trace": pp.TRACE, "bounded": pp.BOUNDED, "occluded": pp.OCCLUDED}[api]
+    cap = pp.plan(kind, pp.launch(facts, 0, 0, 0, cus=ctx.cu_count), n_rays=1 << 40)
+    n = 2 * cap.grid * 256 + BASE + 37
+    plan = pp.plan(kind, pp.launch(facts, 0, 0, 0, cus=ctx.cu_count), n_rays=n)
+    assert plan.rc == 0 and plan.grid == cap.grid == ctx.cu_count * 8
+    assert n > 2 * plan.grid * 256
+    print(f"{name} {api}: n = {n}, grid = {plan.grid}")
+    idx = torch.arange(n, device="cuda") % BASE
+    to, td, tt = (x[idx].contiguous() for x in _cuda(o, d, tm))
+    if api == "occluded":
+        got = {"occluded": scene.occluded(to, td, tmax=tt).view(torch.uint8)}
+        exp = {"occluded": wocc.astype(np.uint8)}
+    else:
+        got = scene.intersect(to, td, full=True, tmax=None if api == "trace" else tt)
+        exp = {k: want[k].view(np.int32) if want[k].dtype == np.uint32 else want[k] for k in FULL}
+    assert ctx.last_kernels() == [pp.name(plan)]
+    tail = np.arange(n - 8192, n) % BASE
+    for k, e in exp.items():
+        g = got[k]
+        assert g.shape[0] == n
+        a = g.view(torch.int32) if g.dtype == torch.float32 else g
+        (te,) = _cuda(e.view(np.int32) if e.dtype == F else e)
+        bad = (a != te[idx]).reshape(n, -1).any(dim=1)
+        assert not bool(bad.any()), f"{k}: {int(bad.sum())} rows, first {int(torch.nonzero(bad)[0])}"
+        assert np.array_equal(a[-8192:].cpu().numpy(), (e.view(np.int32) if e.dtype == F else e)[tail]), k
+
+
+@pytest.mark.parametrize("name", ["teapot", "group"])
+def test_nullable_outputs(ctx, oracle, name):
+    """mp_trace_rays_bounded through the C ABI with only d_prim, only d_normal and only d_instance non-NULL: that array as the
+    full call writes it, and a guard region behind it untouched."""
+    import torch
+
+    scene, _, o, d = _make(name, ctx, oracle)
+    o, d = o[:BASE], d[:BASE]
+    unb = scene._oracle.trace_bounded(o, d)
+    tm = _mixed_bounds(unb["t"], unb["prim"] != NO, np.random.default_rng(14))
+    to, td, tt = _cuda(o, d, tm)
+    full = scene.intersect(to, td, full=True, tmax=tt)
+    assert name != "group" or int(full["instance"].max()) > 0
+    oc, dc_ = to.t().contiguous(), td.t().contiguous()
+    guard = 1024
+    for field in ("prim", "normal", "instance"):
+        ref = full[field]
+        buf = torch.full((ref.numel() + guard,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+        hits = _lib.HitsSoA()
+        setattr(hits, "d_" + field, buf.data_ptr())
+        _lib.check(_lib.lib().mp_trace_rays_bounded(ctx.handle, scene.handle, *[x.data_ptr() for x in (oc[0], oc[1], oc[2], dc_[0], dc_[1], dc_[2])],
+                                                    tt.data_ptr(), BASE, C.byref(hits), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        assert torch.equal(buf[:ref.numel()], ref.reshape(-1).view(torch.int32)), field
+        assert bool((buf[ref.numel():] == 0x5A5A5A5A).all()), field
 
 
 @pytest.mark.parametrize("n", [0, 1, 63, 65, 1000, 4099])

@@ -165,20 +165,12 @@ def _bounds(ts, mx):
             np.nextafter(mx, F(np.inf))]
 
 
-@pytest.mark.parametrize("name", ["atrium:0.05", "atrium:0.1", "soup_5000", "two_clusters"])
-def test_bounded_model_walk_facts(name):
-    """Facts 1-5 of include/minipath_hip.h and occluded == bounded hit, on the model walk (see the module docstring)."""
-    host = _host(name)
-    wide, wroot, _, _ = host.device_tree()
-    lit, lroot, _, _ = host.device_tree(literal=True)
-    info = host.info()
-    bmin, bmax = np.array(list(info.bbox_min), F), np.array(list(info.bbox_max), F)
-    tris_of = _tris(host, lit)
-    unb = lambda l: F(np.inf) if l.size == 0 else l.min()  # noqa: E731
+MODEL_SCENES = ["atrium:0.05", "atrium:0.1", "soup_5000", "two_clusters"]
 
-    def tris_min(link, o, d):  # test_device_tree_cpu._walk's interface: the leaf's smallest valid t
-        return unb(tris_of(link, o, d))
 
+def _model_rays(lit, bmin, bmax):
+    """the 120 rays of the model tests: around and inside the box, zero direction components, origins on box planes, rays aimed
+    at leaf boxes"""
     rng = np.random.default_rng(9)
     ext = bmax - bmin
     n = 120
@@ -196,6 +188,25 @@ def test_bounded_model_walk_facts(name):
         bx = leaves[rng.integers(0, leaves.shape[0])]
         tgt = bx[:3] + (bx[3:] - bx[:3]) * rng.random(3).astype(F)
         d[k] = (tgt - o[k]) / np.linalg.norm(tgt - o[k])
+    return o, d
+
+
+@pytest.mark.parametrize("name", MODEL_SCENES)
+def test_bounded_model_walk_facts(name):
+    """Facts 1-5 of include/minipath_hip.h and occluded == bounded hit, on the model walk (see the module docstring)."""
+    host = _host(name)
+    wide, wroot, _, _ = host.device_tree()
+    lit, lroot, _, _ = host.device_tree(literal=True)
+    info = host.info()
+    bmin, bmax = np.array(list(info.bbox_min), F), np.array(list(info.bbox_max), F)
+    tris_of = _tris(host, lit)
+    unb = lambda l: F(np.inf) if l.size == 0 else l.min()  # noqa: E731
+
+    def tris_min(link, o, d):  # test_device_tree_cpu._walk's interface: the leaf's smallest valid t
+        return unb(tris_of(link, o, d))
+
+    o, d = _model_rays(lit, bmin, bmax)
+    n = o.shape[0]
     checked = {"hit": 0, "miss": 0, "band": 0}
     for k in range(n):
         seq_u, tu, _ = _walk(lit, lroot, tris_min, o[k], d[k])
