@@ -10,9 +10,10 @@ from .screen_block import ScreenBlock, tile_ordering  # noqa: F401
 from .scene import Context, Instances, ObjectGroup, Scene, Sphere, TriangleBvh  # noqa: F401
 from .renderer import (RenderProgress, RenderProgressSnapshot, RenderSettings, render, render_multi, render_tile,  # noqa: F401
                        FrameRenderer, MultiDeviceFrame)
+from .denoise import AtrousDenoiser  # noqa: F401  (denoise/libminipath_denoise.so is loaded on first use, not here)
 
 __all__ = [
-    "AovPlanes", "AovPlanesEx", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
+    "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
     "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "Sphere", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]

@@ -1,0 +1,172 @@
+"""Edge-avoiding a-trous denoiser over the feature planes (include/minipath_denoise.h, denoise/libminipath_denoise.so).
+
+A library of its own beside libminipath_hip.so: it filters image-major [h, w, 4] float32 planes as FrameRenderer.untile /
+untile_plane produce them and needs no Context and no scene.  It is loaded on first use, so ``import minipath_amd`` works where
+only libminipath_hip.so was built; there is no other compute path (a missing library raises).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+
+from ._lib import MP_OK, MinipathError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+# MINIPATH_DENOISE_SO: experiment builds of the same library (kernel variants under measurement); default = the in-tree build
+DENOISE_SO_PATH = os.environ.get("MINIPATH_DENOISE_SO") or os.path.join(_HERE, "denoise", "libminipath_denoise.so")
+
+MPD_FLAG_DEMODULATE_ALBEDO = 1
+MPD_MAX_ITERATIONS = 8
+
+
+class DenoiseSettings(C.Structure):
+    """mpd_settings."""
+
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32),
+                ("sigma_normal_pow2", C.c_float), ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float), ("flags", C.c_uint32)]
+
+
+# name -> (restype, argtypes); every symbol include/minipath_denoise.h declares
+SIGNATURES = {
+    "mpd_last_error": (C.c_char_p, []),
+    "mpd_settings_size": (C.c_uint32, []),
+    "mpd_scratch_floats": (C.c_size_t, [C.POINTER(DenoiseSettings), C.c_int]),
+    "mpd_atrous": (C.c_int, [C.c_int, C.POINTER(DenoiseSettings)] + [C.c_void_p] * 8),
+    "mpd_variance_from_moments": (C.c_int, [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 4),
+    "mpd_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+}
+
+_lib = None
+
+
+def lib() -> C.CDLL:
+    """Load libminipath_denoise.so.  Fails loudly when it has not been built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(DENOISE_SO_PATH):
+            raise ImportError(f"{DENOISE_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- the denoiser has no CPU fallback")
+        try:
+            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
+        except ImportError:
+            pass
+        L = C.CDLL(DENOISE_SO_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _lib = L
+    return _lib
+
+
+def check(rc: int) -> None:
+    if rc != MP_OK:
+        msg = lib().mpd_last_error()
+        raise MinipathError(rc, msg.decode() if msg else "")
+
+
+def last_kernels() -> list:
+    """mpd_last_kernels: the kernels of the calling thread's last launching call, distinct names in launch order."""
+    need = C.c_size_t()
+    check(lib().mpd_last_kernels(None, 0, C.byref(need)))
+    buf = C.create_string_buffer(need.value + 1)
+    check(lib().mpd_last_kernels(buf, need.value + 1, None))
+    return [n for n in buf.value.decode().split("\n") if n]
+
+
+class AtrousDenoiser:
+    """The filter of include/minipath_denoise.h for one resolution (width, height) on one device; owns the scratch planes.
+
+    iterations passes with tap spacing 1, 2, 4, ...; the normal weight is max(0, n_p . n_q) squared sigma_normal_pow2 times, the
+    depth weight 1 / (1 + (|t_p - t_q| / (sigma_depth * spacing))^2), the luminance weight 1 / (1 + (|l_p - l_q| / den)^2) with
+    den = sigma_luminance (sums of r + g + b) or, with a variance plane, sigma_luminance standard deviations of the pixel.
+    sigma_depth is in the scene's length unit per pixel of spacing; the defaults suit scenes a few units across, seen as in the tests.
+    demodulate_albedo: filter colour / albedo and multiply the albedo back (keeps texture detail out of the filter).
+
+        fr = mp.FrameRenderer(scene, camera, settings)
+        planes = fr.new_aov_planes(ids=False, shade_sq=True)
+        fr.render_aov_pass(planes)                                   # the guides of the beauty frame's primary hits
+        beauty = fr.untile(fr.render(), want_u8=False)[0]            # [h, w, 4], any max_depth
+        dn = mp.AtrousDenoiser(settings.resolution, fr.device, demodulate_albedo=True)
+        clean = dn.denoise(beauty, fr.untile_plane(planes["normal"]), albedo=fr.untile_plane(planes["albedo"]))
+        # the first-hit shade with its own variance:
+        var = dn.variance_from_moments(fr.untile_plane(planes["shade"]), fr.untile_plane(planes["shade_sq"]), settings.sample_count)
+        shade, shade_var = dn.denoise(fr.untile_plane(planes["shade"]), fr.untile_plane(planes["normal"]), variance=var)
+    """
+
+    def __init__(self, resolution, device=0, iterations: int = 5, sigma_normal_pow2: int = 7, sigma_depth: float = 0.2,
+                 sigma_luminance: float = 1.5, demodulate_albedo: bool = False, scratch=None):
+        import torch
+
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("the denoiser runs on the GPU")
+        self.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.width, self.height = int(resolution[0]), int(resolution[1])
+        self.settings = DenoiseSettings(C.sizeof(DenoiseSettings), self.width, self.height, int(iterations), float(sigma_normal_pow2),
+                                        float(sigma_depth), float(sigma_luminance), MPD_FLAG_DEMODULATE_ALBEDO if demodulate_albedo else 0)
+        if lib().mpd_scratch_floats(C.byref(self.settings), 0) == 0:
+            check(lib().mpd_atrous(self.device_id, C.byref(self.settings), *([None] * 8)))  # raises with the library's reason
+        self._owns_scratch = scratch is None
+        self._scratch = scratch  # a caller's float32 tensor of scratch_floats(...) elements, or allocated on first use
+
+    def scratch_floats(self, with_variance: bool) -> int:
+        return int(lib().mpd_scratch_floats(C.byref(self.settings), 1 if with_variance else 0))
+
+    def _stream(self):
+        import torch
+
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _plane(self, t, name):
+        import torch
+
+        if t is None:
+            return None
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.device.index == self.device_id
+                and tuple(t.shape) == (self.height, self.width, 4) and t.is_contiguous()):
+            raise ValueError(f"{name}: a contiguous float32 [{self.height}, {self.width}, 4] tensor on {self.device} is expected")
+        return t
+
+    def denoise(self, color, normal_depth, albedo=None, variance=None, out=None, variance_out=None):
+        """mpd_atrous on the current torch stream: `out`, or (`out`, `variance_out`) when a variance plane is given.  The planes
+        are image-major [h, w, 4] float32: colour {r, g, b, alpha} (alpha 0 = a miss, passed through), the "normal" plane
+        {n.x, n.y, n.z, t}, "albedo" (needed with demodulate_albedo), variance {v, -, -, -}.  The inputs are only read.  `out` /
+        `variance_out`: tensors to write into instead of new ones."""
+        import torch
+
+        color, normal_depth = self._plane(color, "color"), self._plane(normal_depth, "normal_depth")
+        albedo, variance = self._plane(albedo, "albedo"), self._plane(variance, "variance")
+        if color is None or normal_depth is None:
+            raise ValueError("color and normal_depth are required")
+        need = self.scratch_floats(variance is not None)
+        if self._scratch is None or (self._owns_scratch and self._scratch.numel() < need):
+            self._scratch, self._owns_scratch = torch.empty(need, dtype=torch.float32, device=self.device), True
+        if self._scratch.numel() < need:
+            raise ValueError(f"scratch: {need} floats are needed")
+        if not (self._scratch.dtype == torch.float32 and self._scratch.is_contiguous() and self._scratch.device.index == self.device_id):
+            raise ValueError("scratch: a contiguous float32 tensor on the denoiser's device is expected")
+        out = torch.empty_like(color) if out is None else self._plane(out, "out")
+        if variance is not None and variance_out is None:
+            variance_out = torch.empty_like(color)
+        variance_out = self._plane(variance_out, "variance_out")
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        check(lib().mpd_atrous(self.device_id, C.byref(self.settings), ptr(color), ptr(normal_depth), ptr(albedo), ptr(variance),
+                               self._scratch.data_ptr(), ptr(out), ptr(variance_out), self._stream()))
+        return out if variance is None else (out, variance_out)
+
+    def variance_from_moments(self, shade, shade_sq, sample_count: int, out=None):
+        """mpd_variance_from_moments on the current torch stream: the variance of each pixel's mean {v, 0, 0, 0} from the "shade"
+        and "shade_sq" planes of render_aov_pass() after sample_count samples (untiled)."""
+        import torch
+
+        shade, shade_sq = self._plane(shade, "shade"), self._plane(shade_sq, "shade_sq")
+        if shade is None or shade_sq is None:
+            raise ValueError("shade and shade_sq are required")
+        out = torch.empty_like(shade) if out is None else self._plane(out, "out")
+        check(lib().mpd_variance_from_moments(self.device_id, self.width, self.height, int(sample_count), shade.data_ptr(),
+                                              shade_sq.data_ptr(), out.data_ptr(), self._stream()))
+        return out
+
+    def last_kernels(self) -> list:
+        """The kernels the calling thread's last launching denoiser call launched (mpd_last_kernels)."""
+        return last_kernels()

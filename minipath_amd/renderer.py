@@ -260,7 +260,15 @@ def render_tile(scene: Scene, sampler: CameraSampler, settings: RenderSettings, 
 class FrameRenderer:
     """Throughput path: renders a list of tiles into a tile-major HBM buffer in ONE launch on the current torch
     stream (mp_render_tiles_device) and scatters them into an image (mp_untile).  Used by bench.py and by the
-    multi-GPU driver; torch only provides the device memory and the stream."""
+    multi-GPU driver; torch only provides the device memory and the stream.
+
+    Denoising a frame with its feature planes (minipath_amd.denoise.AtrousDenoiser, a library of its own):
+
+        planes = fr.new_aov_planes(ids=False)
+        fr.render_aov_pass(planes)                                    # "shade", "normal", "albedo" of the primary hits
+        beauty = fr.untile(fr.render(), want_u8=False)[0]
+        dn = AtrousDenoiser(settings.resolution, fr.device, demodulate_albedo=True)
+        clean = dn.denoise(beauty, fr.untile_plane(planes["normal"]), albedo=fr.untile_plane(planes["albedo"]))"""
 
     def __init__(self, scene: Scene, camera: Camera, settings: RenderSettings, tiles: Optional[Sequence[ScreenBlock]] = None,
                  tile_buf=None):
