@@ -351,7 +351,7 @@ int mp_trace_rays(mp_ctx *ctx, const mp_scene *scene, const float *d_ox, const f
  *                    any-hit walk does: both accept their first hit in the same leaf, or neither ever does.  occluded ==
  *                    (bounded prim != MP_NO_PRIM) holds EXACTLY, for every ray and every tmax, boundary values included.  Which
  *                    triangle stopped the walk is not part of the result.
- * Consequences (t* = mp_trace_rays' distance; the arguments are in minipath_amd/csrc/kernels.hip above query_rays_kernel):
+ * Consequences (t* = mp_trace_rays' distance; the arguments are in minipath_amd/csrc/kernels_queries.hip above query_rays_kernel):
  *   1. d_tmax == NULL or tmax >= FLT_MAX: the same bits as mp_trace_rays in every mp_hits_soa field.
  *   2. The unbounded query misses, or t* >= b: the bounded query misses.
  *   3. The bounded query hits at t: t < b, and t* <= t unless the ray crosses two boxes of the band described in 4.

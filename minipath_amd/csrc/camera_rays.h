@@ -1,5 +1,5 @@
 // A camera ray from its film point and lens point: the arithmetic of CameraSampler::sample_ray (camera.rs:178-191) after its random
-// draws, and Ray::new.  A header of its own because two callers must compute the very same f32 values: sample_ray_rng (kernels.hip),
+// draws, and Ray::new.  A header of its own because two callers must compute the very same f32 values: sample_ray_rng (wave_common.h),
 // which feeds it the sample's draws, and the mask cache's corner rays (mask_cache_begin_unit, mask_cache.h), which feed it the
 // corners of a work unit's footprint.  Device code only.
 #pragma once
@@ -20,7 +20,7 @@ __device__ __forceinline__ void ray_new(float ox, float oy, float oz, float dx, 
     rm::ray_dir(dx, dy, dz, r.dx, r.dy, r.dz, r.ix, r.iy, r.iz);
 }
 // CameraSampler::sample_ray camera.rs:178-191 from the film point (film_u, film_v) and the lens point lens_radius * (x1, x2) on, in
-// the two halves that sample_ray_rng (kernels.hip) puts around its lens draw
+// the two halves that sample_ray_rng (wave_common.h) puts around its lens draw
 __device__ __forceinline__ void camera_film(const mp_camera_sampler& s, float film_u, float film_v, float (&f)[3]) {
     float fv = film_v * s.pixel_scale, fu = film_u * s.pixel_scale;
     f[0] = s.film_origin_offset[0] + s.up[0] * fv - s.right[0] * fu;

@@ -505,7 +505,7 @@ uint32_t pass_samples(const mp_settings& st) {
     return st.pass_count ? st.pass_count : st.sample_count - st.pass_begin;
 }
 
-// One record of mp_ctx_last_kernels: the launchers note their kernels in a list of the calling thread (kernels.hip: MP_LAUNCH); the
+// One record of mp_ctx_last_kernels: the launchers note their kernels in a list of the calling thread (family_launch.h: MP_LAUNCH); the
 // outermost scope on a thread empties that list when it opens and, if anything was launched, files it with the context when it
 // closes.  Entry points nest (mp_render_tile calls mp_render_tiles_device): the inner scopes do nothing.
 struct LaunchScope {
@@ -821,7 +821,7 @@ int mp_scene_from_arrays(mp_ctx* ctx, const mp_bvh_desc* desc, mp_scene** out) {
 
 namespace {
 
-// UnitQuaternion * Vector3, the operation order of the oracle and of the device code (kernels.hip: quat_rotate)
+// UnitQuaternion * Vector3, the operation order of the oracle and of the device code (group_walk.h: quat_rotate)
 void quat_rotate_host(const float q[4], const float v[3], float out[3]) {
     const float tx = (q[1] * v[2] - q[2] * v[1]) * 2.0f, ty = (q[2] * v[0] - q[0] * v[2]) * 2.0f, tz = (q[0] * v[1] - q[1] * v[0]) * 2.0f;
     const float cx = q[1] * tz - q[2] * ty, cy = q[2] * tx - q[0] * tz, cz = q[0] * ty - q[1] * tx;

@@ -1,9 +1,12 @@
-// Every kernel instantiation libminipath_hip.so can launch, written down once.  The list generates the ids the launch plans
-// (launch_plan.h) return, the names mp_ctx_last_kernels reports -- the kernel with its template arguments as the row writes them --
-// and the one switch of kernels.hip that records the name and launches.  No HIP header: the planning source includes it too.
+// Every kernel instantiation libminipath_hip.so can launch, written down once, as one sub-table per kernel family.  The list
+// generates the ids the launch plans (launch_plan.h) return, the names mp_ctx_last_kernels reports -- the kernel with its template
+// arguments as the row writes them -- and the switch that records the name and launches (family_launch.h), which every translation
+// unit expands over the sub-tables of its own kernels: kernels_queries.hip over the ray queries, kernels.hip over the others until
+// they move into units of their own.  No HIP header: the planning source includes it too.
 //
-// A row is X(id, kernel).  Templates stand in the order the launchers have always named them: the compiler emits device code in the
-// order of first use, so moving a row moves its kernel inside the code object.
+// A row is X(id, kernel).  MP_KERNEL_TABLE is the sub-tables in the order the ids have always had.  Templates stand in the order the
+// launchers have always named them: the compiler emits device code in the order of first use, so moving a row moves its kernel
+// inside its unit's code object (and nothing in any other unit's).
 #pragma once
 
 #ifndef MP_MCACHE_WPE
@@ -11,7 +14,7 @@
 #endif
 
 // clang-format off
-#define MP_KERNEL_TABLE(X)                                                                          \
+#define MP_KERNELS_PATHS(X)                                                                         \
     /* path extension: pooled <NSUB>, then <S, OBJ, RGB[, MCACHE]> */                               \
     X(K_PATHS_POOLED_4,        render_paths_pooled_kernel<4>)                                       \
     X(K_PATHS_POOLED_2,        render_paths_pooled_kernel<2>)                                       \
@@ -32,7 +35,9 @@
     X(K_PATHS_1_OBJ_RGB,       render_paths_kernel<1, true, true>)                                  \
     X(K_PATHS_1_OBJ_GREY,      render_paths_kernel<1, true, false>)                                 \
     X(K_PATHS_1_RGB,           render_paths_kernel<1, false, true>)                                 \
-    X(K_PATHS_1_GREY,          render_paths_kernel<1, false, false>)                                \
+    X(K_PATHS_1_GREY,          render_paths_kernel<1, false, false>)
+
+#define MP_KERNELS_TILES(X)                                                                         \
     /* 8-lane groups <S, OBJ>, two rays per lane <W> */                                             \
     X(K_GROUPS_OBJ,            render_tiles_kernel<1, true>)                                        \
     X(K_GROUPS,                render_tiles_kernel<1, false>)                                       \
@@ -64,6 +69,9 @@
     X(K_PACKET_2,              render_tiles_packet_kernel<2, false, 7>)                             \
     X(K_PACKET_1_LDS,          render_tiles_packet_kernel<1, true, 7>)                              \
     X(K_PACKET_1,              render_tiles_packet_kernel<1, false, 7>)                             \
+    /* (end of the fused tiles) */
+
+#define MP_KERNELS_AOV(X)                                                                           \
     /* feature planes <S, LDS_STACK, W[, OBJ[, MCACHE]]> */                                         \
     X(K_AOV_16_CACHED,         render_aov_packet_kernel<16, false, 8, false, true>)                 \
     X(K_AOV_4_CACHED,          render_aov_packet_kernel<4, false, 8, false, true>)                  \
@@ -75,7 +83,9 @@
     X(K_AOV_1_LDS,             render_aov_packet_kernel<1, true, 8>)                                \
     X(K_AOV_16,                render_aov_packet_kernel<16, false, 8>)                              \
     X(K_AOV_4,                 render_aov_packet_kernel<4, false, 8>)                               \
-    X(K_AOV_1,                 render_aov_packet_kernel<1, false, 8>)                               \
+    X(K_AOV_1,                 render_aov_packet_kernel<1, false, 8>)
+
+#define MP_KERNELS_STAGED(X)                                                                        \
     /* staged path evaluation: camera <LDS_STACK, OBJ>, vertex <NCHAN, OBJ>, trace <OBJ> */         \
     X(K_WF_CAMERA_LDS_OBJ,     wf_camera_kernel<true, true>)                                        \
     X(K_WF_CAMERA_OBJ,         wf_camera_kernel<false, true>)                                       \
@@ -89,19 +99,27 @@
     X(K_WF_SCATTER,            wf_scatter_kernel)                                                   \
     X(K_WF_TRACE_OBJ,          wf_trace_groups_kernel<true>)                                        \
     X(K_WF_TRACE,              wf_trace_groups_kernel<false>)                                       \
-    X(K_WF_ACCUMULATE,         wf_accumulate_kernel)                                                \
+    X(K_WF_ACCUMULATE,         wf_accumulate_kernel)
+
+// kernels_queries.hip
+#define MP_KERNELS_QUERIES(X)                                                                       \
     /* ray queries <OBJ[, MODE]> */                                                                 \
     X(K_TRACE_OBJ,             trace_rays_kernel<true>)                                             \
     X(K_TRACE,                 trace_rays_kernel<false>)                                            \
     X(K_QUERY_ANY_OBJ,         query_rays_kernel<true, kAnyHit>)                                    \
     X(K_QUERY_ANY,             query_rays_kernel<false, kAnyHit>)                                   \
     X(K_QUERY_BOUNDED_OBJ,     query_rays_kernel<true, kBounded>)                                   \
-    X(K_QUERY_BOUNDED,         query_rays_kernel<false, kBounded>)                                  \
+    X(K_QUERY_BOUNDED,         query_rays_kernel<false, kBounded>)
+
+#define MP_KERNELS_UTILITIES(X)                                                                     \
     /* utilities */                                                                                 \
     X(K_SET_U64,               set_u64_kernel)                                                      \
     X(K_GENERATE_RAYS,         generate_rays_kernel)                                                \
     X(K_UNTILE,                untile_kernel)                                                       \
     X(K_QUANTISE,              quantise_kernel)
+
+#define MP_KERNEL_TABLE(X) \
+    MP_KERNELS_PATHS(X) MP_KERNELS_TILES(X) MP_KERNELS_AOV(X) MP_KERNELS_STAGED(X) MP_KERNELS_QUERIES(X) MP_KERNELS_UTILITIES(X)
 // clang-format on
 
 namespace mp {

@@ -10,6 +10,11 @@
 // Arithmetic contract: f32, compiled with -ffp-contract=off; fused multiply-adds only where the reference writes
 // mul_add / mul_sub (util/simba.rs:57-67); IEEE division and sqrt; no fast-math.  The results are bit-identical to
 // the CPU oracle's.
+//
+// Translation units.  The kernel families are being moved into units of their own, one family at a time, each over the device
+// headers it needs and each with its own sub-table of kernel_table.h: so far the ray queries (kernels_queries.hip over group_walk.h
+// and wave_common.h).  This file holds the families that have not moved yet, the utility kernels, and what stays here for good: the
+// launch_* entry points of mp_internal.h and the launch record (family_launch.h is what the other units share with it).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +25,7 @@
 
 #include "launch_plan.h"
 #include "mp_internal.h"
+#include "family_launch.h"
 #include "ray_math.h"
 
 #ifdef MP_PROF_MISSES  // profiling builds only (tools/build_variant.sh): slow-path calls of the mask cache, read by mp_prof_read
@@ -31,487 +37,10 @@ __device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask build
 #define MP_PROF_COUNT(i) do { if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_prof[i], 1ull); } while (0)
 #endif
 #include "mask_cache.h"
+#include "group_walk.h"
 
 namespace mp {
 namespace {
-
-// the mask-cache predicates and the per-ray helpers they share with the walk (mask_cache.h)
-using namespace mc;
-
-constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
-constexpr int kQueueFloats = 6 * 64;  // ox,oy,oz,dx,dy,dz (unit direction) x 64 slots ; hit (t,prim,u,v) aliases rows 0..3
-
-// set bits of a wave mask below this lane (v_mbcnt: no per-lane mask register to keep)
-__device__ __forceinline__ int rank_below(uint64_t m) {
-    return static_cast<int>(__builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(m >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(m), 0u)));
-}
-
-// Global memory written by some lanes of ONE wavefront and read by others (the pooled path kernel's ray queue): the wave's
-// outstanding stores are waited for (workgroup-scope release / acquire; the vector L1 of a CU is coherent for its own waves).
-__device__ __forceinline__ void wave_mem_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// ---- 8-lane group collectives on DPP (no LDS traffic) ---------------------------------------------------------
-// row_half_mirror (0x141) pairs lane i with 7-i inside every group of 8; quad_perm [1,0,3,2] (0xB1) and
-// [2,3,0,1] (0x4E) finish the butterfly inside each quad.  All 8 lanes end with the group's reduction.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
-    return static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, 0xF, 0xF, false));
-}
-// Minimum of hit distances (>= 0, possibly -0.0, never NaN): on those the signed-integer order of the bit patterns is the float
-// order (-0.0 below +0.0, as v_min_f32 has it), and v_min_i32 takes the DPP operand directly (no canonicalising v_max).
-__device__ __forceinline__ float group_min_t(float v) {
-    int k = __float_as_int(v);
-    k = min(k, __builtin_amdgcn_update_dpp(0, k, 0x141, 0xF, 0xF, false));
-    k = min(k, __builtin_amdgcn_update_dpp(0, k, 0xB1, 0xF, 0xF, false));
-    k = min(k, __builtin_amdgcn_update_dpp(0, k, 0x4E, 0xF, 0xF, false));
-    return __int_as_float(k);
-}
-__device__ __forceinline__ uint32_t group_min_u(uint32_t v) {
-    v = min(v, dpp_u<0x141>(v));
-    v = min(v, dpp_u<0xB1>(v));
-    v = min(v, dpp_u<0x4E>(v));
-    return v;
-}
-
-// ---- RNG: rand 0.9.3 SmallRng = Xoshiro256++ (seeded mode, include/minipath_hip.h), on 32-bit halves (ray_math.h) -------
-using rm::Rng;
-using rm::rng_seed;
-using rm::rng_value0_1;
-using rm::unit_disc;
-__device__ __forceinline__ void rng_zero(Rng& r) { r.s0 = r.s1 = r.s2 = r.s3 = rm::U64{0u, 0u}; }
-
-struct RayGen {
-    mp_camera_sampler s;
-    float jitter_scale;  // UniformFloat::new_inclusive(-0.5, 0.5).scale, computed on the host
-    uint32_t width, spp;
-    uint64_t seed;  // mix(settings.seed), see mixed_seed()
-};
-
-// CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream (ADVANCE = false: nothing is drawn from it afterwards);
-// ray_new and the arithmetic from the film point on are camera_rays.h's (camera_film, camera_lens_ray): the mask cache's corner rays share it
-template <bool ADVANCE = true>
-__device__ __forceinline__ void sample_ray_rng(const RayGen& P, uint32_t x, uint32_t y, Rng& rng, Ray& r) {
-    float film_u = static_cast<float>(x) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
-    float film_v = static_cast<float>(y) + (rng_value0_1(rng) * P.jitter_scale + (-0.5f));
-    float f[3];
-    camera_film(P.s, film_u, film_v, f);
-    float x1, x2;
-    unit_disc<ADVANCE>(rng, x1, x2);
-    camera_lens_ray(P.s, f, x1, x2, r);
-}
-
-// key = mix(seed) + sample index; `P.seed` already holds mix(seed) (mixed_seed(), on the host)
-__device__ __forceinline__ uint64_t sample_key(const RayGen& P, uint32_t x, uint32_t y, uint32_t sample) {
-    return P.seed + ((static_cast<uint64_t>(y) * P.width + x) * P.spp + sample);
-}
-
-// seeded per (pixel, sample): include/minipath_hip.h "Seeded mode"
-__device__ __forceinline__ void sample_ray(const RayGen& P, uint32_t x, uint32_t y, uint32_t sample, Ray& r) {
-    Rng rng;
-    rng_seed(rng, sample_key(P, x, y, sample));
-    sample_ray_rng<false>(P, x, y, rng, r);
-}
-
-// ---- traversal --------------------------------------------------------------------------------------------------
-// Lane masks straight from the compare unit (v_cmp writes the 64-bit mask; no bool -> int -> ballot round trip, which costs two
-// VALU per use): LLVM CmpInst predicate numbers.
-constexpr int kFcmpOGT = 2, kFcmpOGE = 3, kFcmpOLT = 4, kFcmpOLE = 5;
-__device__ __forceinline__ uint64_t mask_gt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOGT); }
-__device__ __forceinline__ uint64_t mask_lt(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOLT); }
-__device__ __forceinline__ uint64_t mask_le(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOLE); }
-__device__ __forceinline__ uint64_t mask_ge(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, kFcmpOGE); }
-
-// Traces `nrays` rays held in the wave's LDS queue `q` (rows ox,oy,oz,dx,dy,dz; slot = column).
-// On return rows 0..3 of each slot hold the closest hit: t (f32::MAX on miss), prim (bits), u, v.
-// impl Object for TriangleBvh::intersect, ray_bvh_intersection.rs:26-96, for 8 rays at a time.
-// BFE: the count of passing children below a lane from v_bfe_u32 instead of a loop-invariant mask register (one VGPR less, one
-// VALU more per node step): pays in trace_rays_kernel, which sits at the 64-VGPR cap, and costs 0.5 % in render_paths_kernel.
-// QS = queue stride = ray slots.  QS == 64: the wave's LDS queue (rows ox,oy,oz,dx,dy,dz; the hit aliases rows 0..3; inverse
-// directions computed here, one slot per lane).  QS > 64: the pooled path kernel's queue in global memory (rows 0..5 origin and
-// direction, 6..8 inverse direction as Ray::new has it, 9..12 the hit: the rays are needed again for shading).
-// MODE (ray queries, include/minipath_hip.h "Bounded and occlusion queries"; QS == 64 only): kClosest = the walk above, best.t
-// starts at f32::MAX; kBounded = the same walk with best.t -- and every lane's candidate tl -- starting at the ray's bound b
-// (`pb` = b of queue slot `lane`, fetched by the group that pulls the slot, like the inverse direction); kAnyHit = that walk
-// ended at the first packet in which a lane accepts a triangle (t < b): row 1 of the slot then holds only prim = 0 (occluded)
-// or MP_NO_PRIM.  Before its first hit the bounded walk's best.t is b, so both walks push, cull and test exactly alike up to
-// that packet: occluded == (the bounded walk hits), for every ray and bound.
-enum { kClosest = 0, kBounded = 1, kAnyHit = 2 };
-template <bool PATCH_NAN, bool BFE, int QS = 64, int MODE = kClosest>
-__device__ __forceinline__ void trace_wave_impl(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base,
-                                                int nrays, float pb = FLT_MAX) {
-    static_assert(MODE == kClosest || QS == 64, "ray queries run on the wave's LDS queue");
-    constexpr int HB = QS == 64 ? 0 : 9;  // first hit row
-    const int lane = static_cast<int>(threadIdx.x) & 63;
-    const int g = lane >> 3, li = lane & 7;
-    uint2* stack = stack_base + g * sc.stack_cap;
-    const uint32_t lanes_below = (1u << li) - 1u;
-
-    int slot = -1, sp = 0, head = 0;
-    uint32_t pk = 0, pk_end = 0, seq = 0;
-    float ox = 0, oy = 0, oz = 0, dx = 0, dy = 0, dz = 0, ix = 0, iy = 0, iz = 0;
-    // Lane li fetches child li / triangle li as whole 16-byte words from the AoS copies (two loads per node, three per packet)
-    // PATCH_NAN = some queued ray has an infinite inverse direction component: literal reference tree; otherwise the wide tree
-    // (thin nodes absorbed into their parents: same hits for finite inverses, device_tree.cpp)
-    const float4* __restrict__ nodes4 = reinterpret_cast<const float4*>(PATCH_NAN ? sc.nodes_lit : sc.nodes_aos);
-    const uint32_t root = PATCH_NAN ? sc.root_lit : sc.root;
-    const float* __restrict__ tris = sc.tris_aos;
-    float best_t = FLT_MAX;                 // best.t, group-uniform (ray_bvh_intersection.rs:34-37)
-    float tl = FLT_MAX, ul = 0, vl = 0;     // this lane's earliest closest candidate
-    uint32_t pkl = kNoPrim, seql = 0;
-    // inv_direction as Ray::new has it (geometry/mod.rs:49-53) for the ray in queue slot `lane`, computed ONCE here for all 64
-    // slots in parallel (three IEEE divisions per call instead of three per refill step); a group fetches its ray's inverse with
-    // ds_bpermute when it pulls the ray.  Not queued in LDS: three rows more per wave would cost a resident wave on deep trees.
-    float pix = 0.0f, piy = 0.0f, piz = 0.0f;
-    if (QS == 64) {
-        const float qx = q[3 * 64 + lane], qy = q[4 * 64 + lane], qz = q[5 * 64 + lane];
-        pix = (qx == 0.0f) ? INFINITY : 1.0f / qx; piy = (qy == 0.0f) ? INFINITY : 1.0f / qy; piz = (qz == 0.0f) ? INFINITY : 1.0f / qz;
-    }
-
-    for (;;) {
-        // -- ray finished: resolve the winner among the 8 lanes.  The reference takes candidates in (packet visit
-        //    order, ascending lane) and replaces on strict `<` (:118-136, :59): the winner is the earliest candidate
-        //    that attains the minimum t.  Every lane kept its own earliest minimum; ties across lanes go to the
-        //    smaller (visit sequence, lane).
-        if (MODE == kAnyHit && slot >= 0 && sp == 0 && pk == pk_end) {
-            if (li == 0) q[1 * 64 + slot] = as_f(pkl);  // 0 = occluded (set where the walk stopped), MP_NO_PRIM = not
-            slot = -1;
-        }
-        if (MODE != kAnyHit && slot >= 0 && sp == 0 && pk == pk_end) {
-            float tmin = group_min_t(tl);
-            uint32_t key = (pkl != kNoPrim && tl == tmin) ? ((seql << 3) | static_cast<uint32_t>(li)) : 0xFFFFFFFFu;
-            uint32_t kmin = group_min_u(key);
-            // winner's lane, recomputed from the lane id where it is needed (ds_bpermute takes a byte address: lane * 4)
-            const int wl4 = (((static_cast<int>(threadIdx.x) & 56) | static_cast<int>(kmin & 7u))) << 2;
-            const float wu = __int_as_float(__builtin_amdgcn_ds_bpermute(wl4, __float_as_int(ul)));
-            const float wv = __int_as_float(__builtin_amdgcn_ds_bpermute(wl4, __float_as_int(vl)));
-            const uint32_t wp = static_cast<uint32_t>(__builtin_amdgcn_ds_bpermute(wl4, static_cast<int>(pkl)));
-            if (li == 0) {
-                bool hit = kmin != 0xFFFFFFFFu;
-                q[(HB + 0) * QS + slot] = hit ? tmin : FLT_MAX;
-                q[(HB + 1) * QS + slot] = as_f(hit ? (wp * 8u + (kmin & 7u)) : kNoPrim);
-                q[(HB + 2) * QS + slot] = wu;
-                q[(HB + 3) * QS + slot] = wv;
-            }
-            slot = -1;
-        }
-        // -- idle groups pull the next rays of the queue (wave-uniform head, no atomics)
-        uint64_t idle = __ballot(slot < 0);
-        if (idle != 0) {
-            // the mask of the groups below this one is needed once per ray: recomputed here (3 VALU) rather than kept in -- or spilled
-            // from -- two registers for the whole walk
-            int g_ = g;
-            asm volatile("" : "+v"(g_));
-            const uint64_t groups_below = (1ull << (g_ * 8)) - 1ull;
-            uint64_t gm = idle & 0x0101010101010101ull;
-            int mine = head + __popcll(gm & groups_below);
-            head += __popcll(gm);
-            // (ds_bpermute reads the source lane's register whether or not that lane is enabled; an out-of-range `mine` wraps)
-            float fix = 0.0f, fiy = 0.0f, fiz = 0.0f, fb = FLT_MAX;
-            if (QS == 64) { fix = __shfl(pix, mine & 63); fiy = __shfl(piy, mine & 63); fiz = __shfl(piz, mine & 63); }
-            if (MODE != kClosest) fb = __shfl(pb, mine & 63);
-            if (slot < 0 && mine < nrays) {
-                slot = mine;
-                ox = q[0 * QS + mine]; oy = q[1 * QS + mine]; oz = q[2 * QS + mine];
-                dx = q[3 * QS + mine]; dy = q[4 * QS + mine]; dz = q[5 * QS + mine];
-                if (QS != 64) { fix = q[6 * QS + mine]; fiy = q[7 * QS + mine]; fiz = q[8 * QS + mine]; }
-                ix = fix; iy = fiy; iz = fiz;
-                best_t = fb; tl = fb; ul = 0; vl = 0; pkl = kNoPrim; seql = 0; seq = 0;  // :34-37, best.t = b
-                pk = pk_end = 0;
-                sp = 1;
-                if (li == 0) stack[0] = make_uint2(root, as_u(-INFINITY));  // :28-32
-            }
-            if (__ballot(slot >= 0) == 0) break;
-        }
-        wave_lds_sync();
-        // -- A: groups with no pending packet pop one stack entry (:39-62)
-        if (slot >= 0 && pk == pk_end) {
-            sp--;
-            uint2 e = stack[sp];
-            float node_t1 = as_f(e.y);
-            if (!(node_t1 > best_t)) {  // :40-44
-                uint32_t link = e.x;
-                if ((link & 63u) == 0u) {  // device link (mp_internal.h): inner = index << 6
-                    // InnerNode::intersect :149-162 ; lane li = child li.  Child boxes are stored decompressed
-                    // (SURVEY A.4 box chain evaluated once on the host), so the slab test starts directly.
-                    // (a uniform base + a 32-bit byte offset per lane: link = node << 6, a node is 256 bytes, a child record 32)
-                    const float4* cp = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(nodes4) + ((link << 2) | (static_cast<uint32_t>(li) << 5)));
-                    const float4 c0 = cp[0], c1 = cp[1];  // {min.xyz, max.x} {max.yz, link, -}
-                    const uint32_t child = as_u(c1.z);
-                    // aabb.rs:254-284
-                    float ax = (c0.x - ox) * ix, ay = (c0.y - oy) * iy, az = (c0.z - oz) * iz;
-                    float cx = (c0.w - ox) * ix, cy = (c1.x - oy) * iy, cz = (c1.y - oz) * iz;
-                    // NaN (0 * inf) -> -inf on the min side, +inf on the max side (aabb.rs:262-267): maxNum / minNum return the
-                    // other operand for a NaN and the value itself otherwise, one instruction each and no branch.  Only a ray with
-                    // a zero direction component (infinite inverse) can produce one: queues without such a ray run the variant
-                    // without the six patches (trace_wave)
-                    if (PATCH_NAN) {
-                        ax = fmaxf(ax, -INFINITY); ay = fmaxf(ay, -INFINITY); az = fmaxf(az, -INFINITY);
-                        cx = fminf(cx, INFINITY); cy = fminf(cy, INFINITY); cz = fminf(cz, INFINITY);
-                    }
-                    const float t1 = fmaxf(fmaxf(fminf(ax, cx), 0.0f), fmaxf(fminf(ay, cy), fminf(az, cz)));
-                    const float t2 = fminf(fminf(fmaxf(ax, cx), best_t), fminf(fmaxf(ay, cy), fmaxf(az, cz)));
-                    // Null links are skipped at pop in the reference (:49).  The lane mask comes straight from the compare unit;
-                    // lanes outside this branch contribute garbage bits to other groups' bytes, which are never looked at
-                    const uint64_t okm = mask_le(t1, t2) & __builtin_amdgcn_uicmp(child, MP_LINK_NULL, 33);  // 33 = ICMP_NE
-                    const bool ok = __builtin_amdgcn_inverse_ballot_w64(okm);
-                    uint32_t m = static_cast<uint32_t>(okm >> (g * 8)) & 0xFFu;
-                    const uint32_t below = BFE ? __builtin_amdgcn_ubfe(m, 0u, static_cast<uint32_t>(li)) : (m & lanes_below);
-                    if (ok) stack[sp + __popc(below)] = make_uint2(child, as_u(t1));  // ascending lane :161
-                    sp += __popc(m);
-                } else {
-                    pk = link >> 6;  // Leaf :56-62 ; device link = first packet << 6 | real triangles
-                    pk_end = pk + (((link & 63u) + 7u) >> 3);
-                }
-            }
-        }
-        // -- B: one leaf packet per iteration (:104-140) ; lane li = triangle li
-        if (slot >= 0 && pk < pk_end) {
-            // 36-byte records: v0, e1, e2 ; a uniform base + a 32-bit byte offset per lane (fewer than 2^32 / 288 packets: upload_scene)
-            const uint32_t toff = ((pk * 9u) << 5) + static_cast<uint32_t>(li) * 36u;
-            const float* tp = reinterpret_cast<const float*>(reinterpret_cast<const char*>(tris) + toff);
-            const float v0x = tp[0], v0y = tp[1], v0z = tp[2], e1x = tp[3], e1y = tp[4], e1z = tp[5], e2x = tp[6], e2y = tp[7], e2z = tp[8];
-            // triangle.rs:183-217
-            float hx = fms(dy, e2z, dz * e2y), hy = fms(dz, e2x, dx * e2z), hz = fms(dx, e2y, dy * e2x);
-            float det = fma_dot(e1x, e1y, e1z, hx, hy, hz);
-            float inv_det = 1.0f / det;
-            float sx = ox - v0x, sy = oy - v0y, sz = oz - v0z;
-            float u = inv_det * fma_dot(sx, sy, sz, hx, hy, hz);
-            float qx = fms(sy, e1z, sz * e1y), qy = fms(sz, e1x, sx * e1z), qz = fms(sx, e1y, sy * e1x);
-            float v = inv_det * fma_dot(dx, dy, dz, qx, qy, qz);
-            float t = inv_det * fma_dot(e2x, e2y, e2z, qx, qy, qz);
-            bool valid = (u >= 0.0f) & (v >= 0.0f) & ((u + v) <= 1.0f) & (t >= 0.0f) & (t <= best_t);  // :125
-            if (MODE == kAnyHit) {
-                // tl == best_t == b for the whole walk: a set bit in the group's byte of the ballot is :59's `hit.t < best.t` for
-                // some triangle of this packet.  The ray is done: empty stack, no pending packet, the group pulls the next ray.
-                if ((__ballot(valid && t < tl) >> (g * 8)) & 0xFFull) { sp = 0; pk = pk_end; pkl = 0u; }
-                else pk++;
-                continue;
-            }
-            if (valid && t < tl) { tl = t; ul = u; vl = v; pkl = pk; seql = seq; }
-            seq++;
-            pk++;
-            if (pk == pk_end) best_t = group_min_t(tl);  // `if hit.t < best.t { best = hit }` :59-61
-        }
-    }
-    wave_lds_sync();
-}
-
-// A queue without a ray that has an infinite inverse direction component (a zero -- or, denormals being kept, a tiny --
-// direction component: geometry/mod.rs:49-53) cannot produce 0 * inf in the slab test: it runs the variant without the NaN
-// patches (six VALU per node step less) on the wide tree.  Wave-uniform choice per call.
-template <bool BFE = false, int MODE = kClosest>
-__device__ __forceinline__ void trace_wave(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base, int nrays,
-                                           float pb = FLT_MAX) {
-    const int lane = static_cast<int>(threadIdx.x) & 63;
-    const float qx = q[3 * 64 + lane], qy = q[4 * 64 + lane], qz = q[5 * 64 + lane];
-    const float ix = (qx == 0.0f) ? INFINITY : 1.0f / qx, iy = (qy == 0.0f) ? INFINITY : 1.0f / qy, iz = (qz == 0.0f) ? INFINITY : 1.0f / qz;
-    const bool inf = lane < nrays && (fabsf(ix) == INFINITY || fabsf(iy) == INFINITY || fabsf(iz) == INFINITY);
-    if (__ballot(inf) != 0) trace_wave_impl<true, BFE, 64, MODE>(sc, q, stack_base, nrays, pb);
-    else trace_wave_impl<false, BFE, 64, MODE>(sc, q, stack_base, nrays, pb);
-}
-
-// ... and for the pooled path kernel's queue of QS > 64 slots in global memory (inverse directions in rows 6..8)
-template <int QS>
-__device__ __forceinline__ void trace_wave_pool(const DevScene& sc, float* __restrict__ q, uint2* __restrict__ stack_base, int nrays) {
-    int lane = static_cast<int>(threadIdx.x) & 63;
-    asm volatile("" : "+v"(lane));  // (re-derived per call: the twelve row addresses below are not worth registers -- or spill slots -- across the kernel)
-    bool inf = false;
-#pragma unroll
-    for (int k = 0; k < QS / 64; k++) {
-        const int slot = lane + 64 * k;
-        if (slot < nrays)
-            inf = inf || fabsf(q[6 * QS + slot]) == INFINITY || fabsf(q[7 * QS + slot]) == INFINITY || fabsf(q[8 * QS + slot]) == INFINITY;
-    }
-    if (__ballot(inf) != 0) trace_wave_impl<true, true, QS>(sc, q, stack_base, nrays);
-    else trace_wave_impl<false, true, QS>(sc, q, stack_base, nrays);
-}
-
-// Exact conservative pre-test against the union of the root node's child boxes (DevScene::pre_min/pre_max): every
-// child box C lies inside that union U, and the slab interval of C is contained in the slab interval of U in
-// floating point too (IEEE subtraction and multiplication are monotone, and the NaN patches of aabb.rs:262-267 map
-// to the containing infinities), so a ray whose U interval is empty pushes no child of the root and is a miss.
-__device__ __forceinline__ bool may_hit_scene(const DevScene& sc, const Ray& r) {
-    if (!sc.has_pre) return true;
-    float ax = (sc.pre_min[0] - r.ox) * r.ix, ay = (sc.pre_min[1] - r.oy) * r.iy, az = (sc.pre_min[2] - r.oz) * r.iz;
-    float cx = (sc.pre_max[0] - r.ox) * r.ix, cy = (sc.pre_max[1] - r.oy) * r.iy, cz = (sc.pre_max[2] - r.oz) * r.iz;
-    ax = (ax != ax) ? -INFINITY : ax; ay = (ay != ay) ? -INFINITY : ay; az = (az != az) ? -INFINITY : az;
-    cx = (cx != cx) ? INFINITY : cx; cy = (cy != cy) ? INFINITY : cy; cz = (cz != cz) ? INFINITY : cz;
-    float lox = fminf(ax, cx), loy = fminf(ay, cy), loz = fminf(az, cz);
-    float hix = fmaxf(ax, cx), hiy = fmaxf(ay, cy), hiz = fmaxf(az, cz);
-    float t1 = fmaxf(fmaxf(lox, 0.0f), fmaxf(loy, loz));
-    float t2 = fminf(fminf(hix, FLT_MAX), fminf(hiy, hiz));
-    return t1 <= t2;
-}
-
-// Hit resolve + shade: tail of intersect (ray_bvh_intersection.rs:66-95) and render_sample (worker.rs:59-65).
-// Returns |dot(ray.direction, normal)|.
-// Returns TriangleShadingData.material of the triangle (mod.rs:44; 0 for everything the reference builds).
-__device__ __forceinline__ uint32_t resolve_normal(const DevScene& sc, uint32_t prim, float u, float v, float n[3]) {
-    const float4* sh = reinterpret_cast<const float4*>(sc.shade) + static_cast<size_t>(prim) * 3;
-    float4 a = sh[0], b = sh[1], c = sh[2];
-    float nx, ny, nz;
-    if (as_u(c.y) != 0u) {
-        // flat: Triangle::normal (triangle.rs:141-144), unfused cross of the decompressed edges
-        const float* tp = sc.tris_aos + static_cast<size_t>(prim) * kTriDwords;
-        float e1x = tp[3], e1y = tp[4], e1z = tp[5], e2x = tp[6], e2y = tp[7], e2z = tp[8];
-        nx = e1y * e2z - e1z * e2y;
-        ny = e1z * e2x - e1x * e2z;
-        nz = e1x * e2y - e1y * e2x;
-    } else {
-        float w = 1.0f - u - v;  // triangle.rs:235-236
-        nx = a.x * w + a.w * u + b.z * v;
-        ny = a.y * w + b.x * u + b.w * v;
-        nz = a.z * w + b.y * u + c.x * v;
-    }
-    float len = sqrtf(nx * nx + ny * ny + nz * nz);
-    n[0] = nx / len; n[1] = ny / len; n[2] = nz / len;
-    return as_u(c.z);
-}
-
-// impl Object for Sphere::intersect, scene/primitives.rs:16-48 (lane-parallel; n = unit normal at the hit)
-__device__ __forceinline__ bool sphere_intersect(const DevScene& sc, const Ray& r, float& t, float n[3]) {
-    const float ocx = r.ox - sc.sphere_center[0], ocy = r.oy - sc.sphere_center[1], ocz = r.oz - sc.sphere_center[2];
-    const float b = ocx * r.dx + ocy * r.dy + ocz * r.dz;
-    const float c = (ocx * ocx + ocy * ocy + ocz * ocz) - sc.sphere_radius * sc.sphere_radius;
-    const float disc = b * b - c;
-    if (disc < 0.0f) return false;
-    const float sq = sqrtf(disc);
-    const float t1 = -b - sq, t2 = -b + sq;
-    if (t1 > 0.0f) t = t1;
-    else if (t2 > 0.0f) t = t2;
-    else return false;
-    const float px = r.ox + r.dx * t, py = r.oy + r.dy * t, pz = r.oz + r.dz * t;
-    const float nx = px - sc.sphere_center[0], ny = py - sc.sphere_center[1], nz = pz - sc.sphere_center[2];
-    const float len = sqrtf(nx * nx + ny * ny + nz * nz);
-    n[0] = nx / len; n[1] = ny / len; n[2] = nz / len;
-    return true;
-}
-
-// Build-defined object group (mp_scene_group / mp_scene_instances): the scene seen as member k -- the member's own traversal
-// arrays under the group's material table and stack bound.  k is wave-uniform in the pass over member k (scalar loads) and per
-// lane when a lane shades the member its ray hit.
-__device__ __forceinline__ void object_scene(const DevScene& sc, uint32_t k, DevScene& sk) {
-    sk = sc;
-    const DevObject& o = sc.objects[k];
-    sk.shade = o.shade; sk.nodes_aos = o.nodes_aos; sk.nodes_lit = o.nodes_lit; sk.tris_aos = o.tris_aos; sk.vidx = o.vidx; sk.vtex = o.vtex;
-    sk.root = o.root; sk.root_lit = o.root_lit; sk.has_pre = o.has_pre;
-    sk.kind = o.kind; sk.sphere_radius = o.sphere_radius;
-    for (int i = 0; i < 3; i++) { sk.pre_min[i] = o.pre_min[i]; sk.pre_max[i] = o.pre_max[i]; sk.sphere_center[i] = o.sphere_center[i]; }
-}
-// UnitQuaternion * Vector3 as the oracle (and nalgebra) evaluate it: t = 2 * (qv x v); v' = t * w + (qv x t) + v, unfused
-__device__ __forceinline__ void quat_rotate(float qi, float qj, float qk, float qw, float vx, float vy, float vz, float& ox,
-                                            float& oy, float& oz) {
-    const float tx = (qj * vz - qk * vy) * 2.0f, ty = (qk * vx - qi * vz) * 2.0f, tz = (qi * vy - qj * vx) * 2.0f;
-    const float cx = qj * tz - qk * ty, cy = qk * tx - qi * tz, cz = qi * ty - qj * tx;
-    ox = tx * qw + cx + vx; oy = ty * qw + cy + vy; oz = tz * qw + cz + vz;
-}
-// ... and the ray in member k's frame: origin - translation, then (rotated members) origin and direction through the inverse
-// rotation; the direction is not re-normalised (t stays the world ray's), inv_direction by Ray::new's rule (geometry/mod.rs:49-53)
-__device__ __forceinline__ void object_ray(const DevScene& sc, uint32_t k, const Ray& r, Ray& rk) {
-    const DevObject& o = sc.objects[k];
-    rk = r;
-    rk.ox = r.ox - o.t[0]; rk.oy = r.oy - o.t[1]; rk.oz = r.oz - o.t[2];
-    if (o.rotated) {
-        const float qi = -o.q[0], qj = -o.q[1], qk = -o.q[2], qw = o.q[3];
-        const float vx = rk.ox, vy = rk.oy, vz = rk.oz;
-        quat_rotate(qi, qj, qk, qw, vx, vy, vz, rk.ox, rk.oy, rk.oz);
-        quat_rotate(qi, qj, qk, qw, r.dx, r.dy, r.dz, rk.dx, rk.dy, rk.dz);
-        rk.ix = (rk.dx == 0.0f) ? INFINITY : 1.0f / rk.dx;
-        rk.iy = (rk.dy == 0.0f) ? INFINITY : 1.0f / rk.dy;
-        rk.iz = (rk.dz == 0.0f) ? INFINITY : 1.0f / rk.dz;
-    }
-}
-
-struct GroupHit {
-    float t, u, v;
-    uint32_t prim, inst;
-};
-
-// Closest hit of the wave's rays (one per lane, `act` = lane holds a ray) with the group walk: compaction of the lanes whose ray
-// can reach the object into the wave's ray queue, trace_wave, results back to the lanes.  OBJ: once per member of the object
-// group, in order, closest wins with a strict `<` (the first member keeps ties).
-// MODE != kClosest (ray queries): `b` = this lane's bound (> 0, finite; include/minipath_hip.h).  Every member is walked with
-// best.t = b and h.t starts at b, so a member's hit counts only below b and the combination is today's; h.t = f32::MAX again
-// for a miss.  kAnyHit: a lane whose ray is occluded is not queued for later members; h.prim = 0 marks it.
-template <bool OBJ, bool BFE = false, int MODE = kClosest>
-__device__ __forceinline__ void trace_objects(const DevScene& sc, const Ray& r, bool act, float* __restrict__ q,
-                                              uint2* __restrict__ stack, GroupHit& h, float b = FLT_MAX) {
-    h.t = MODE == kClosest ? FLT_MAX : b; h.u = h.v = 0.0f; h.prim = kNoPrim; h.inst = 0u;
-    auto pass = [&](const DevScene& sk, const Ray& rk, uint32_t k) {
-        const bool open = act && (MODE != kAnyHit || h.prim == kNoPrim);
-        if (OBJ && sk.kind == 1u) {  // a Sphere member (scene/primitives.rs:16-48): lane-parallel, no walk; prim 0
-            float ts, nn[3];
-            if (open && sphere_intersect(sk, rk, ts, nn) && ts < h.t) { h.t = ts; h.prim = 0u; h.u = h.v = 0.0f; h.inst = k; }
-            return;
-        }
-        const bool queued = open && may_hit_scene(sk, rk);
-        const uint64_t am = __ballot(queued);
-        const int n = __popcll(am), rank = rank_below(am);
-        if (queued) {
-            q[0 * 64 + rank] = rk.ox; q[1 * 64 + rank] = rk.oy; q[2 * 64 + rank] = rk.oz;
-            q[3 * 64 + rank] = rk.dx; q[4 * 64 + rank] = rk.dy; q[5 * 64 + rank] = rk.dz;
-        }
-        float pb = FLT_MAX;
-        if (MODE != kClosest) {
-            // the bound of queue slot `lane` into lane `lane` (ds_permute = scatter): queued lanes send to their rank, the others to
-            // the slots above n, so that every lane has exactly one sender
-            const int dst = queued ? rank : n + (static_cast<int>(threadIdx.x & 63) - rank);
-            pb = __int_as_float(__builtin_amdgcn_ds_permute(dst << 2, __float_as_int(b)));
-        }
-        wave_lds_sync();
-        trace_wave<BFE, MODE>(sk, q, stack, n, pb);
-        if (queued) {
-            const uint32_t prim = as_u(q[1 * 64 + rank]);
-            if (MODE == kAnyHit) {
-                if (prim != kNoPrim) { h.prim = 0u; h.inst = k; }
-            } else {
-                const float t = q[0 * 64 + rank];
-                if (prim != kNoPrim && t < h.t) { h.t = t; h.prim = prim; h.u = q[2 * 64 + rank]; h.v = q[3 * 64 + rank]; h.inst = k; }
-            }
-        }
-        wave_lds_sync();
-    };
-    if (!OBJ) {
-        pass(sc, r, 0u);
-    } else {
-        for (uint32_t k = 0; k < sc.inst_count; k++) {
-            DevScene sk;
-            Ray rk;
-            object_scene(sc, k, sk);
-            object_ray(sc, k, r, rk);
-            pass(sk, rk, k);
-        }
-    }
-    if (MODE != kClosest && h.prim == kNoPrim) h.t = FLT_MAX;
-}
-
-// Normal and material id of a hit on member `inst` of an object group (r = the world ray).  A Sphere member's normal is that of
-// its intersect, evaluated again on the ray in the member's frame (same operations, same bits); material 0 (primitives.rs:40-46).
-__device__ __forceinline__ uint32_t object_normal(const DevScene& sc, uint32_t inst, const Ray& r, uint32_t prim, float u, float v,
-                                                  float n[3]) {
-    DevScene so;
-    object_scene(sc, inst, so);
-    uint32_t mat = 0u;
-    if (so.kind == 1u) {
-        Ray rk;
-        object_ray(sc, inst, r, rk);
-        float t;
-        sphere_intersect(so, rk, t, n);
-    } else {
-        mat = resolve_normal(so, prim, u, v, n);
-    }
-    const DevObject& o = sc.objects[inst];
-    if (o.rotated) quat_rotate(o.q[0], o.q[1], o.q[2], o.q[3], n[0], n[1], n[2], n[0], n[1], n[2]);  // back into the world frame
-    return mat;
-}
 
 // ---- fused tile render: Worker::render_tile (worker.rs:32-49) for a list of tiles -----------------------------
 struct RenderParams {
@@ -587,11 +116,6 @@ __device__ __forceinline__ void pixel_state_store(const RenderParams& P, size_t 
 // did not fit was spilled to VGPR lanes and scratch (round 2: 78 SGPR + 4 VGPR spills in the packet kernel, 67 + 29 and 104 B of
 // scratch in the path kernel).
 typedef const __attribute__((address_space(4))) RenderParams* kparams_t;
-template <class T>
-__device__ __forceinline__ const T& kernarg_view(const __attribute__((address_space(4))) T* kp) {
-    asm volatile("" : "+s"(kp));
-    return *(const T*)kp;
-}
 __device__ __forceinline__ const RenderParams& params_view(kparams_t kp) { return kernarg_view<RenderParams>(kp); }
 #define MP_KERNEL_PARAMS kparams_t KP = (kparams_t)__builtin_amdgcn_kernarg_segment_ptr()
 
@@ -2568,225 +2092,6 @@ __global__ __launch_bounds__(256) void wf_accumulate_kernel(WfParams P) {
     }
 }
 
-// ---- batched Object::intersect over SoA ray streams (ray_bvh_intersection.rs:26-96) -------------------------
-struct TraceParams {
-    DevScene scene;
-    const float *ox, *oy, *oz, *dx, *dy, *dz;
-    uint64_t n;
-    mp_hits_soa hits;
-    uint32_t lds_per_wave;
-};
-
-// The stores of trace_rays_kernel's HitRecord, for query_rays_kernel.  (trace_rays_kernel keeps its own inline copy: calling these
-// changes its scalar register allocation, and its code stays as measured.)
-// HitRecord of a Sphere scene for ray i (primitives.rs:40-46): {t, point, normal, material 0, texture_coords origin}; a miss
-// writes t = f32::MAX, MP_NO_PRIM and zeros
-__device__ __forceinline__ void store_sphere_hit(const TraceParams& P, uint64_t i, const Ray& r, bool hit, float t, const float nn[3]) {
-    if (P.hits.d_t) P.hits.d_t[i] = t;
-    if (P.hits.d_prim) P.hits.d_prim[i] = hit ? 0u : kNoPrim;
-    if (P.hits.d_u) P.hits.d_u[i] = 0.0f;
-    if (P.hits.d_v) P.hits.d_v[i] = 0.0f;
-    for (int k = 0; k < 3; k++) {
-        const float o = k == 0 ? r.ox : k == 1 ? r.oy : r.oz, d = k == 0 ? r.dx : k == 1 ? r.dy : r.dz;
-        if (P.hits.d_point) P.hits.d_point[i * 3 + k] = hit ? o + d * t : 0.0f;
-        if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = hit ? nn[k] : 0.0f;
-        if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = 0.0f;
-    }
-    if (P.hits.d_material) P.hits.d_material[i] = 0u;
-    if (P.hits.d_instance) P.hits.d_instance[i] = 0u;
-}
-
-// HitRecord of ray i from the group walk's closest hit (ray_bvh_intersection.rs:66-95); a miss writes zeros beyond t / prim
-template <bool OBJ>
-__device__ __forceinline__ void store_group_hit(const TraceParams& P, uint64_t i, const GroupHit& gh) {
-    const float t = gh.t, u = gh.u, v = gh.v;
-    const uint32_t prim = gh.prim, inst = gh.inst;
-    if (P.hits.d_t) P.hits.d_t[i] = t;
-    if (P.hits.d_prim) P.hits.d_prim[i] = prim;
-    if (P.hits.d_u) P.hits.d_u[i] = u;
-    if (P.hits.d_v) P.hits.d_v[i] = v;
-    if (P.hits.d_point || P.hits.d_normal || P.hits.d_tex || P.hits.d_material) {
-        float pt[3] = {0, 0, 0}, nn[3] = {0, 0, 0}, tx[3] = {0, 0, 0};
-        uint32_t mat = 0;  // HitRecord.material (geometry/mod.rs:78)
-        if (prim != kNoPrim) {
-            Ray r;  // rebuilt here so that no ray registers stay live across the walk
-            ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r);
-            DevScene so = P.scene;  // the member the ray hit (its normals, texture coordinates, material ids)
-            if (OBJ) object_scene(P.scene, inst, so);
-            mat = OBJ ? object_normal(P.scene, inst, r, prim, u, v, nn) : resolve_normal(so, prim, u, v, nn);
-            pt[0] = r.ox + r.dx * t; pt[1] = r.oy + r.dy * t; pt[2] = r.oz + r.dz * t;  // geometry/mod.rs:56-58
-            if (!OBJ || so.kind == 0u) {  // a Sphere member's texture_coords are the origin (primitives.rs:45)
-                const uint32_t* vi = so.vidx + static_cast<size_t>(prim) * 3;
-                const float *t0 = so.vtex + 3 * static_cast<size_t>(vi[0]), *t1 = so.vtex + 3 * static_cast<size_t>(vi[1]),
-                            *t2 = so.vtex + 3 * static_cast<size_t>(vi[2]);
-                float w = 1.0f - u - v;
-                for (int k = 0; k < 3; k++) tx[k] = t0[k] * w + t1[k] * u + t2[k] * v;
-            }
-        }
-        for (int k = 0; k < 3; k++) {
-            if (P.hits.d_point) P.hits.d_point[i * 3 + k] = pt[k];
-            if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = nn[k];
-            if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = tx[k];
-        }
-        if (P.hits.d_material) P.hits.d_material[i] = mat;
-    }
-    if (P.hits.d_instance) P.hits.d_instance[i] = inst;
-}
-
-template <bool OBJ>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void trace_rays_kernel(TraceParams) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    typedef const __attribute__((address_space(4))) TraceParams* ktrace_t;
-    ktrace_t KP = (ktrace_t)__builtin_amdgcn_kernarg_segment_ptr();  // TraceParams through short-lived views (see params_view)
-    const TraceParams& P0 = kernarg_view<TraceParams>(KP);
-    const int lane = static_cast<int>(threadIdx.x) & 63, wave = static_cast<int>(threadIdx.x) >> 6;
-    float* q = reinterpret_cast<float*>(smem + static_cast<size_t>(wave) * P0.lds_per_wave);
-    uint2* stack = reinterpret_cast<uint2*>(q + kQueueFloats);
-    const uint64_t chunks = (P0.n + 63) / 64;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
-    for (uint64_t chunk = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave; chunk < chunks; chunk += stride) {
-        const TraceParams& P = kernarg_view<TraceParams>(KP);  // one view per chunk of 64 rays
-        const uint64_t i = chunk * 64 + lane;
-        const bool act = i < P.n;
-        Ray r0;
-        r0.ox = r0.oy = r0.oz = r0.dx = r0.dy = r0.dz = r0.ix = r0.iy = r0.iz = 0.0f;
-        if (act) ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r0);
-        if (P.scene.kind == 1u) {
-            const Ray& r = r0;  // Sphere: HitRecord{t, point, normal, material 0, texture_coords origin} (primitives.rs:40-46)
-            if (act) {
-                float t = FLT_MAX, nn[3] = {0, 0, 0};
-                const bool hit = sphere_intersect(P.scene, r, t, nn);
-                if (!hit) t = FLT_MAX;
-                if (P.hits.d_t) P.hits.d_t[i] = t;
-                if (P.hits.d_prim) P.hits.d_prim[i] = hit ? 0u : kNoPrim;
-                if (P.hits.d_u) P.hits.d_u[i] = 0.0f;
-                if (P.hits.d_v) P.hits.d_v[i] = 0.0f;
-                for (int k = 0; k < 3; k++) {
-                    const float o = k == 0 ? r.ox : k == 1 ? r.oy : r.oz, d = k == 0 ? r.dx : k == 1 ? r.dy : r.dz;
-                    if (P.hits.d_point) P.hits.d_point[i * 3 + k] = hit ? o + d * t : 0.0f;
-                    if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = hit ? nn[k] : 0.0f;
-                    if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = 0.0f;
-                }
-                if (P.hits.d_material) P.hits.d_material[i] = 0u;
-                if (P.hits.d_instance) P.hits.d_instance[i] = 0u;
-            }
-            continue;
-        }
-        GroupHit gh;
-        trace_objects<OBJ, true>(P.scene, r0, act, q, stack, gh);
-        const float t = gh.t, u = gh.u, v = gh.v;
-        const uint32_t prim = gh.prim, inst = gh.inst;
-        if (act) {
-            if (P.hits.d_t) P.hits.d_t[i] = t;
-            if (P.hits.d_prim) P.hits.d_prim[i] = prim;
-            if (P.hits.d_u) P.hits.d_u[i] = u;
-            if (P.hits.d_v) P.hits.d_v[i] = v;
-            if (P.hits.d_point || P.hits.d_normal || P.hits.d_tex || P.hits.d_material) {
-                float pt[3] = {0, 0, 0}, nn[3] = {0, 0, 0}, tx[3] = {0, 0, 0};
-                uint32_t mat = 0;  // HitRecord.material (geometry/mod.rs:78)
-                if (prim != kNoPrim) {
-                    Ray r;  // rebuilt here so that no ray registers stay live across the walk
-                    ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r);
-                    DevScene so = P.scene;  // the member the ray hit (its normals, texture coordinates, material ids)
-                    if (OBJ) object_scene(P.scene, inst, so);
-                    mat = OBJ ? object_normal(P.scene, inst, r, prim, u, v, nn) : resolve_normal(so, prim, u, v, nn);
-                    pt[0] = r.ox + r.dx * t; pt[1] = r.oy + r.dy * t; pt[2] = r.oz + r.dz * t;  // geometry/mod.rs:56-58
-                    if (!OBJ || so.kind == 0u) {  // a Sphere member's texture_coords are the origin (primitives.rs:45)
-                        const uint32_t* vi = so.vidx + static_cast<size_t>(prim) * 3;
-                        const float *t0 = so.vtex + 3 * static_cast<size_t>(vi[0]), *t1 = so.vtex + 3 * static_cast<size_t>(vi[1]),
-                                    *t2 = so.vtex + 3 * static_cast<size_t>(vi[2]);
-                        float w = 1.0f - u - v;
-                        for (int k = 0; k < 3; k++) tx[k] = t0[k] * w + t1[k] * u + t2[k] * v;
-                    }
-                }
-                for (int k = 0; k < 3; k++) {
-                    if (P.hits.d_point) P.hits.d_point[i * 3 + k] = pt[k];
-                    if (P.hits.d_normal) P.hits.d_normal[i * 3 + k] = nn[k];
-                    if (P.hits.d_tex) P.hits.d_tex[i * 3 + k] = tx[k];
-                }
-                if (P.hits.d_material) P.hits.d_material[i] = mat;
-            }
-            if (P.hits.d_instance) P.hits.d_instance[i] = inst;
-        }
-    }
-}
-
-// ---- bounded closest hit and occlusion over SoA ray streams (include/minipath_hip.h "Bounded and occlusion queries") ----------
-// trace_rays_kernel with a per-ray bound b = min(tmax, f32::MAX) (d_tmax NULL: f32::MAX): MODE = kBounded writes the HitRecord of
-// the walk with best.t = b (same fields, same miss record as mp_trace_rays), kAnyHit one byte per ray: 1 = that walk hits.
-// A ray with NaN or non-positive tmax is a miss and is not walked.  Same grid, LDS and 8-waves-per-SIMD rules as trace_rays_kernel.
-//
-// Why the facts of include/minipath_hip.h hold (t* = the unbounded walk's distance, W(b) = the walk with best.t starting at b):
-//  1. b = f32::MAX is the unbounded walk's own start: every push, cull, leaf test and acceptance is the same, so are the bits
-//     written (the miss record included: tl = FLT_MAX, no candidate, u = v = 0, t = FLT_MAX).
-//  2. The unbounded walk's best.t starts at f32::MAX >= b and never drops below t* >= b until it ends; W(b)'s never exceeds b.
-//     Every slab limit and pop test of W(b) is therefore at least as strict, so W(b) visits a subset of the unbounded walk's
-//     leaves, in the same relative order (children are pushed in ascending, popped in descending slot order in both).  A
-//     triangle W(b) could accept has t < b <= t* and passes the leaf test in a leaf the unbounded walk visits with best.t >=
-//     t* > t, which would have made its result < t*: there is none, W(b) misses.
-//  3. W(b) accepts only t < b.  While W(b)'s best.t <= the unbounded walk's (true at the start), every box W(b) pushes and pops
-//     the unbounded walk pushes and pops too, and every leaf both visit leaves W(b)'s best.t <= the unbounded walk's; so W(b)'s
-//     result is >= t* unless the unbounded walk accepts a triangle in a leaf that W(b) culled.  That needs a triangle whose
-//     distance lies below its box's floating-point entry (the band of 4), and W(b) then has to accept, in another such box,
-//     a triangle below t*: two band boxes on one ray.  Outside that, t* <= t.
-//  4. If b is at least the slab entry t1 of every box the ray enters, the bound b in t2 = min(exit, best.t) and in the pop
-//     test removes no box that f32::MAX would keep before the first hit; from the first hit on both walks carry the same
-//     best.t (the same leaves were visited with the same candidates).  So W(b) == the unbounded walk when t* < b, and a miss
-//     otherwise (fact 2).
-//  5. The wide tree's argument (device_tree.cpp) uses only that best.t never grows: it holds for any starting value.
-// Occluded == (W(b) hits): the any-hit walk is W(b) up to its first accepting packet (best.t == b in both until then).
-struct QueryParams {
-    TraceParams tr;
-    const float* tmax;
-    uint8_t* occluded;
-};
-
-template <bool OBJ, int MODE>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void query_rays_kernel(QueryParams) {
-    static_assert(MODE == kBounded || MODE == kAnyHit, "a query mode");
-    extern __shared__ __align__(16) unsigned char smem[];
-    typedef const __attribute__((address_space(4))) QueryParams* kquery_t;
-    kquery_t KP = (kquery_t)__builtin_amdgcn_kernarg_segment_ptr();  // QueryParams through short-lived views (see params_view)
-    const QueryParams& P0 = kernarg_view<QueryParams>(KP);
-    const int lane = static_cast<int>(threadIdx.x) & 63, wave = static_cast<int>(threadIdx.x) >> 6;
-    float* q = reinterpret_cast<float*>(smem + static_cast<size_t>(wave) * P0.tr.lds_per_wave);
-    uint2* stack = reinterpret_cast<uint2*>(q + kQueueFloats);
-    const uint64_t chunks = (P0.tr.n + 63) / 64;
-    const uint64_t stride = static_cast<uint64_t>(gridDim.x) * (blockDim.x >> 6);
-    for (uint64_t chunk = static_cast<uint64_t>(blockIdx.x) * (blockDim.x >> 6) + wave; chunk < chunks; chunk += stride) {
-        const QueryParams& Q = kernarg_view<QueryParams>(KP);  // one view per chunk of 64 rays
-        const TraceParams& P = Q.tr;
-        const uint64_t i = chunk * 64 + lane;
-        const bool act = i < P.n;
-        // effective bound: NaN and tmax <= 0 give b = 0 (a miss, not walked); +inf and anything above give f32::MAX
-        float b = 0.0f;
-        if (act) {
-            const float tm = Q.tmax ? Q.tmax[i] : FLT_MAX;
-            b = tm > 0.0f ? fminf(tm, FLT_MAX) : 0.0f;
-        }
-        const bool walk = b > 0.0f;
-        Ray r0;
-        r0.ox = r0.oy = r0.oz = r0.dx = r0.dy = r0.dz = r0.ix = r0.iy = r0.iz = 0.0f;
-        if (walk) ray_new(P.ox[i], P.oy[i], P.oz[i], P.dx[i], P.dy[i], P.dz[i], r0);
-        if (P.scene.kind == 1u) {  // Sphere: a hit counts below b (primitives.rs:16-48)
-            if (act) {
-                float t = FLT_MAX, nn[3] = {0, 0, 0};
-                const bool hit = walk && sphere_intersect(P.scene, r0, t, nn) && t < b;
-                if (!hit) t = FLT_MAX;
-                if (MODE == kAnyHit) Q.occluded[i] = hit ? 1u : 0u;
-                else store_sphere_hit(P, i, r0, hit, t, nn);
-            }
-            continue;
-        }
-        GroupHit gh;
-        trace_objects<OBJ, true, MODE>(P.scene, r0, walk, q, stack, gh, b);
-        if (act) {
-            if (MODE == kAnyHit) Q.occluded[i] = gh.prim != kNoPrim ? 1u : 0u;
-            else store_group_hit<OBJ>(P, i, gh);
-        }
-    }
-}
-
 // ---- CameraSampler::sample_ray batched (camera.rs:176-191) -----------------------------------------------------
 __global__ __launch_bounds__(256) void generate_rays_kernel(RayGen G, mp_block blk, uint32_t sample, float* ox, float* oy,
                                                             float* oz, float* dx, float* dy, float* dz) {
@@ -2879,6 +2184,8 @@ uint64_t mixed_seed(uint64_t seed) {
     return z ^ (z >> 31);
 }
 
+}  // namespace
+
 int check(hipError_t e, const char* what, std::string& err) {
     if (e == hipSuccess) return MP_OK;
     err = std::string(what) + ": " + hipGetErrorString(e);
@@ -2889,44 +2196,26 @@ static_assert(kPlanQueueFloats == kQueueFloats && kPlanMaskCacheDwords == kMaskC
                   kPlanPoolFloatsPerSub == pool_floats_per_wave(1),
               "launch_plan.h sizes the launches with the device code's constants");
 
-// Launch record (diagnostic, mp_ctx_last_kernels) and the one place that launches: launch() notes the row's name -- the kernel with
-// its template arguments as kernel_table.h writes them -- in the calling thread's list and then launches that row's kernel.  The
-// statement that launches is the statement that records: there is no second selection to keep in step.  Distinct names, in launch
-// order; the usual case is a compare against a handful of ids.
+// Launch record (diagnostic, mp_ctx_last_kernels) and the one place that launches: launch() (family_launch.h) notes the row's name --
+// the kernel with its template arguments as kernel_table.h writes them -- in the calling thread's list and then launches that row's
+// kernel.  Distinct names, in launch order; the usual case is a compare against a handful of ids.
+namespace {
 thread_local std::vector<KernelId> t_launched;
-inline void note_launch(KernelId id) {
+}  // namespace
+void note_launch(KernelId id) {
     if (std::find(t_launched.begin(), t_launched.end(), id) == t_launched.end()) t_launched.push_back(id);
 }
-#define MP_LAUNCH(id, kernel, grid, block, lds, stream, ...)               \
-    do {                                                                   \
-        note_launch(id);                                                   \
-        hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
-    } while (0)
 
 int launched(KernelId id, std::string& err) {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? MP_OK : check(e, (std::string(kKernelNames[id]) + " launch").c_str(), err);
 }
 
-// Launches row `id` of the table with these arguments.  A row whose kernel does not take them is not instantiated for them; an id
-// of such a row is a programming error (MP_ERR_INVALID).
-template <class... Args>
-int launch(KernelId id, uint32_t grid, uint32_t block, uint32_t lds, hipStream_t st, std::string& err, const Args&... args) {
-    switch (id) {
-#define MP_X(row, ...)                                                                   \
-    case row:                                                                            \
-        if constexpr (std::is_invocable_v<decltype(&__VA_ARGS__), Args...>) {            \
-            MP_LAUNCH(row, (__VA_ARGS__), dim3(grid), dim3(block), lds, st, args...);    \
-            return launched(row, err);                                                   \
-        }                                                                                \
-        break;
-        MP_KERNEL_TABLE(MP_X)
-#undef MP_X
-        default: break;
-    }
-    err = "kernel table: no such kernel for these arguments";
-    return MP_ERR_INVALID;
-}
+namespace {
+
+// this unit's rows: the families that have no unit of their own yet, and the utilities
+#define MP_KERNELS_HERE(X) MP_KERNELS_PATHS(X) MP_KERNELS_TILES(X) MP_KERNELS_AOV(X) MP_KERNELS_STAGED(X) MP_KERNELS_UTILITIES(X)
+MP_FAMILY_LAUNCHER(MP_KERNELS_HERE)
 
 void fill_raygen(RayGen& G, const mp_camera_sampler& s, uint32_t width, uint32_t spp, uint64_t seed) {
     G.s = s;
@@ -2963,12 +2252,6 @@ void fill_render(RenderParams& P, const RenderLaunch& L, const LaunchPlan& plan)
     P.pool = nullptr;
     P.pool_stride = plan.pool_stride;
     P.lds_per_wave = plan.lds_per_wave;
-}
-
-template <class Plan>
-int refused(const Plan& plan, std::string& err) {
-    err = plan.error;
-    return plan.rc;
 }
 
 int zero_work_queues(const RenderLaunch& L, hipStream_t st, std::string& err) {
@@ -3095,28 +2378,6 @@ int launch_render_paths_wavefront(const RenderLaunch& L, void* stream, std::stri
     (void)hipFreeAsync(ws, st);
     return rc;
 }
-
-namespace {
-// the three ray queries: one plan, one fill; mp_trace_rays launches on the TraceParams alone
-int launch_rays(QueryKind kind, const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
-                const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count, void* stream,
-                std::string& err) {
-    if (n == 0) return MP_OK;
-    const LaunchPlan plan = plan_ray_query(sc, n, cu_count, kind);
-    if (plan.rc) return refused(plan, err);
-    QueryParams P;
-    P.tr.scene = sc;
-    P.tr.ox = ox; P.tr.oy = oy; P.tr.oz = oz; P.tr.dx = dx; P.tr.dy = dy; P.tr.dz = dz;
-    P.tr.n = n;
-    P.tr.hits = hits ? *hits : mp_hits_soa{};
-    P.tr.lds_per_wave = plan.lds_per_wave;
-    P.tmax = tmax;
-    P.occluded = occluded;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (kind == kQueryClosest) return launch(plan.kernel, plan.grid, 256, plan.lds, st, err, P.tr);
-    return launch(plan.kernel, plan.grid, 256, plan.lds, st, err, P);
-}
-}  // namespace
 
 int launch_trace_rays(const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx,
                       const float* dy, const float* dz, uint64_t n, const mp_hits_soa& hits, int cu_count, void* stream,

@@ -60,7 +60,7 @@ def launched(ctx):
     return [k for k in ctx.last_kernels() if k not in EXCLUDED]
 
 
-# launch sites of the test probes, outside kernels.hip and outside the library (libmp_probe.so / libmp_mask_probe.so)
+# launch sites of the test probes, outside family_launch.h and outside the library (libmp_probe.so / libmp_mask_probe.so)
 PROBE_FILES = {
     "probe.hip": "test probe of ray_math.h (tests/test_ray_math_gpu.py): its kernels are the test, not the product",
     "mask_probe.hip": "test probe of mask_cache.h (tests/test_mask_cache_gpu.py): its kernels are the test, not the product",

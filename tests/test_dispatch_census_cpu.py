@@ -1,7 +1,7 @@
 """The dispatch census (no GPU): the kernel table (minipath_amd/csrc/kernel_table.h, read from the built probe libmp_plan_probe.so) is
-exactly the set of rows of tests/dispatch_cases.py, which tests/test_gpu_dispatch_matrix.py runs one by one; kernels.hip launches in
-one place only, the switch the table generates, which records the row's name; and no instantiation of a kernel template is named
-outside the table.  A new instantiation without a parity case, or a case whose instantiation is gone, fails here, on every machine."""
+exactly the set of rows of tests/dispatch_cases.py, which tests/test_gpu_dispatch_matrix.py runs one by one; the library launches
+in one place only, the switch the table generates (family_launch.h), which records the row's name and which every translation unit
+expands over the sub-tables of its own kernels; and no instantiation of a kernel template is named outside the table.  A new instantiation without a parity case, or a case whose instantiation is gone, fails here, on every machine."""
 import ctypes as C
 import os
 import re
@@ -44,30 +44,67 @@ def test_the_case_table_is_the_census():
     assert not [n for n in pp.table() if "MP_" in n or "  " in n]
 
 
+def _device_sources():
+    """the sources with device code: the translation units and the headers they share"""
+    src = _library_sources()
+    return {f: t for f, t in src.items() if f.endswith(".hip") or "__device__" in t or "__global__" in t}
+
+
+def _subtables():
+    """{sub-table macro: [row ids]} and the order MP_KERNEL_TABLE concatenates them in, from kernel_table.h"""
+    text = _library_sources()["kernel_table.h"]
+    subs = {m.group(1): re.findall(r"\bX\((K_\w+),\s*(.*?)\)\s", m.group(2))
+            for m in re.finditer(r"#define (MP_KERNELS_\w+)\(X\)((?:[^\n]*\\\n)*[^\n]*\n)", text)}
+    whole = re.search(r"#define MP_KERNEL_TABLE\(X\)((?:[^\n]*\\\n)*[^\n]*\n)", text).group(1)
+    return subs, re.findall(r"(MP_KERNELS_\w+)\(X\)", whole)
+
+
 def test_no_launch_bypasses_the_record():
     src = _library_sources()
-    text = src["kernels.hip"]
-    raw = [m.start() for m in re.finditer(RAW_LAUNCH, text)]
-    assert len(raw) == 1, "kernels.hip launches only inside the MP_LAUNCH macro"
-    line = text[: raw[0]].count("\n")
+    raw = [(f, m.start()) for f, t in src.items() for m in re.finditer(RAW_LAUNCH, t)]
+    assert len(raw) == 1 and raw[0][0] == "family_launch.h", "the library launches only inside the MP_LAUNCH macro"
+    text = src["family_launch.h"]
+    line = text[: raw[0][1]].count("\n")
     window = "\n".join(text.split("\n")[line - 3: line + 1])
     assert "#define MP_LAUNCH(" in window and "note_launch(id)" in window, "the one raw launch is MP_LAUNCH's own, next to its record"
-    uses = [m.start() for m in re.finditer(r"\bMP_LAUNCH\(", text) if "#define" not in text[text.rfind("\n", 0, m.start()):m.start()]]
-    assert len(uses) == 1, "MP_LAUNCH is used once: by the switch over the table"
-    at = text[: uses[0]].count("\n")
-    around = "\n".join(text.split("\n")[at - 3: at + 6])
-    assert "#define MP_X(row, ...)" in around and "case row:" in around and "MP_KERNEL_TABLE(MP_X)" in around, "... generated from the table, row by row"
-    # the other sources of the library launch nothing
-    for f, t in src.items():
-        if f != "kernels.hip":
-            assert not re.search(RAW_LAUNCH + r"|\bMP_LAUNCH\(", t), f
+    uses = [(f, m.start()) for f, t in src.items() for m in re.finditer(r"\bMP_LAUNCH\(", t)
+            if "#define" not in t[t.rfind("\n", 0, m.start()):m.start()]]
+    assert len(uses) == 1 and uses[0][0] == "family_launch.h", "MP_LAUNCH is used once: by the switch over a sub-table"
+    at = text[: uses[0][1]].count("\n")
+    around = "\n".join(text.split("\n")[at - 3: at + 14])
+    assert "#define MP_LAUNCH_ROW(row, ...)" in around and "case row:" in around and "SUBTABLE(MP_LAUNCH_ROW)" in around, "... generated from the table, row by row"
+    assert len(re.findall(r"\bMP_LAUNCH_ROW\b", "".join(src.values()))) == 2, "the row's case is written once and expanded by MP_FAMILY_LAUNCHER alone"
     for f in dc.PROBE_FILES:
         assert os.path.exists(os.path.join(CSRC, f)), f"{f} is excluded but gone"
 
 
+def test_the_subtables_are_the_table_and_every_unit_launches_its_own():
+    subs, order = _subtables()
+    assert sorted(order) == sorted(subs) and len(order) == len(set(order)), "MP_KERNEL_TABLE is every sub-table once"
+    rows = [r for name in order for r in subs[name]]
+    ids = [i for i, _ in rows]
+    assert len(ids) == len(set(ids)), "... with each row once"
+    assert [k.replace("MP_MCACHE_WPE", "8") for _, k in rows] == pp.table(), "... and it is the table the library was built from, in its order"
+    # every translation unit expands the switch once: over a sub-table, or over a concatenation of sub-tables that it defines itself
+    src = _library_sources()
+    units = {}
+    for f, t in src.items():
+        for name in re.findall(r"^MP_FAMILY_LAUNCHER\((\w+)\)", t, flags=re.M):
+            assert f.endswith(".hip") and f not in units, (f, name)
+            units[f] = [name] if name in subs else re.findall(r"(MP_KERNELS_\w+)\(X\)", re.search(r"#define %s\(X\)([^\n]*)\n" % name, t).group(1))
+    assert len(units) >= 2 and units["kernels_queries.hip"] == ["MP_KERNELS_QUERIES"]
+    # ... every sub-table is expanded exactly once in the library
+    assert sorted(n for names in units.values() for n in names) == sorted(subs), units
+    # ... by the unit that defines the sub-table's kernels, which defines no others
+    for f, names in units.items():
+        kernels = set(re.findall(r"__global__ [^\n]*\bvoid (\w+)\(", src[f]))
+        assert {k.split("<")[0] for n in names for _, k in subs[n]} == kernels, (f, names)
+
+
 def test_kernel_templates_are_instantiated_by_the_table_alone():
     src = _library_sources()
-    templates = set(re.findall(r"^template <[^\n]*>\n__global__ [^\n]*\bvoid (\w+)\(", src["kernels.hip"], flags=re.M))
+    device = "\n".join(_device_sources().values())
+    templates = set(re.findall(r"^template <[^\n]*>\n__global__ [^\n]*\bvoid (\w+)\(", device, flags=re.M))
     assert {"render_tiles_packet_kernel", "render_paths_kernel", "render_aov_packet_kernel", "wf_camera_kernel", "query_rays_kernel"} <= templates
     assert {n.split("<")[0] for n in pp.table() if "<" in n} == templates, "every kernel template has rows, and only kernel templates have arguments"
     for f, t in src.items():

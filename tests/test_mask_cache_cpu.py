@@ -32,15 +32,40 @@ def test_probe_exports_entry_points():
     assert not missing, f"libmp_mask_probe.so does not export {missing}"
 
 
+def _device_sources():
+    """every source of the library with device code but mask_cache.h and the two headers below it (camera_rays.h, ray_math.h): the
+    translation units (kernels*.hip) and the device headers they share"""
+    out = {}
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith((".hip", ".h")) and f not in ("mask_cache.h", "camera_rays.h", "ray_math.h", "mask_probe.hip", "probe.hip"):
+            text = open(os.path.join(CSRC, f)).read()
+            if "__device__" in text or "__global__" in text:
+                out[f] = text
+    return out
+
+
 def test_kernels_take_predicates_from_header():
-    kernels = open(os.path.join(CSRC, "kernels.hip")).read()
+    sources = _device_sources()
+    assert {"kernels.hip", "kernels_queries.hip", "group_walk.h", "wave_common.h"} <= set(sources)
     header = open(os.path.join(CSRC, "mask_cache.h")).read()
     probe = open(os.path.join(CSRC, "mask_probe.hip")).read()
-    assert '#include "mask_cache.h"' in kernels and '#include "mask_cache.h"' in probe
+    assert '#include "mask_cache.h"' in sources["kernels.hip"] and '#include "mask_cache.h"' in sources["wave_common.h"]
+    assert '#include "mask_cache.h"' in probe
     for name in PREDICATES + HELPERS:
         assert _defines(header, name), f"mask_cache.h does not define {name}"
-        assert not _defines(kernels, name), f"kernels.hip defines {name} itself"
+        for f, text in sources.items():
+            assert not _defines(text, name), f"{f} defines {name} itself"
         assert not _defines(probe, name), f"mask_probe.hip defines {name} itself"
+    # a source that uses a predicate or a helper has the header in its includes, directly or through the library's own headers
+    def includes(f, seen):
+        for h in re.findall(r'#include "(\w+\.h)"', open(os.path.join(CSRC, f)).read()):
+            if h not in seen:
+                seen.add(h)
+                includes(h, seen)
+        return seen
+    for f, text in sources.items():
+        if any(re.search(r"\b" + re.escape(n.replace("struct ", "")) + r"\b", text) for n in PREDICATES + HELPERS):
+            assert "mask_cache.h" in includes(f, set()), f"{f} uses the mask cache's code without its header"
     # the walk uses them
     for name in ["mask_cache_ray_ok(", "mask_cache_begin_pass(", "bounds_may_hit<OCT>(", "tri_may_hit(", "slab<"]:
-        assert name in kernels, f"kernels.hip no longer calls {name}"
+        assert name in sources["kernels.hip"], f"kernels.hip no longer calls {name}"

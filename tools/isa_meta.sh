@@ -1,11 +1,15 @@
 #!/bin/bash
-# Per-kernel register / spill / scratch metadata of a gfx950 code object (device-only compile with the Makefile's flags, then the
-# AMDGPU metadata note).  usage: tools/isa_meta.sh [denoise] > profiles/rNN_isa_meta.txt
-#   (no argument)  kernels.hip, the code object of libminipath_hip.so
+# Per-kernel register / spill / scratch metadata of gfx950 code objects (device-only compiles with the Makefile's flags, then the
+# AMDGPU metadata notes).  usage: tools/isa_meta.sh [denoise] > profiles/rNN_isa_meta.txt
+#   (no argument)  the code objects of libminipath_hip.so, one per translation unit (kernels*.hip), as one list sorted by kernel
 #   denoise        ../denoise/atrous.hip, the code object of libminipath_denoise.so -> profiles/denoise/isa_meta.txt
 set -e
 cd "$(dirname "$0")/../minipath_amd/csrc"
-CO=kernels.gfx950.co
-[ "$1" = denoise ] && CO=../denoise/atrous.gfx950.co
-make -s "$CO"
-/opt/rocm/lib/llvm/bin/llvm-readelf --notes "$CO" | python3 ../../tools/isa_meta.py
+if [ "$1" = denoise ]; then
+  make -s ../denoise/atrous.gfx950.co
+  COS=../denoise/atrous.gfx950.co
+else
+  make -s code-objects
+  COS=$(echo kernels*.gfx950.co)
+fi
+for co in $COS; do /opt/rocm/lib/llvm/bin/llvm-readelf --notes "$co"; done | python3 ../../tools/isa_meta.py

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Where do a kernel's scratch (spill) instructions sit?  Disassembles minipath_amd/csrc/kernels.gfx950.co, finds the natural
+"""Where do a kernel's scratch (spill) instructions sit?  Disassembles the library's code objects (minipath_amd/csrc/kernels*.gfx950.co: make code-objects), finds the natural
 loops of the kernel whose mangled name contains argv[1] (backward branches), and prints every scratch_load / scratch_store with
 the number of loops around it and the length of the innermost one.  usage: scratch_in_loops.py KERNEL_SUBSTRING"""
-import re, subprocess, sys, os
-co = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "minipath_amd", "csrc", "kernels.gfx950.co")
-txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", co], capture_output=True, text=True).stdout
+import glob, re, subprocess, sys, os
+cos = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "minipath_amd", "csrc", "kernels*.gfx950.co")))
+txt = "\n".join(subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", co], capture_output=True, text=True).stdout for co in cos)
 fn = None; ins = []
 for line in txt.splitlines():
     m = re.match(r"^([0-9a-f]+) <(.+)>:", line)
