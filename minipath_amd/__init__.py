@@ -11,9 +11,10 @@ from .scene import Context, Instances, ObjectGroup, Scene, Sphere, TriangleBvh  
 from .renderer import (RenderProgress, RenderProgressSnapshot, RenderSettings, render, render_multi, render_tile,  # noqa: F401
                        FrameRenderer, MultiDeviceFrame)
 from .denoise import AtrousDenoiser  # noqa: F401  (denoise/libminipath_denoise.so is loaded on first use, not here)
+from .adaptive import AdaptiveSampler  # noqa: F401  (adaptive/libminipath_adaptive.so is loaded on first use, not here)
 
 __all__ = [
-    "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
+    "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
     "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "Sphere", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]
