@@ -17,7 +17,15 @@ Why each row selects its kernel follows plan_render_tiles / plan_render_aov / pl
 frames of the matrix (72 x 40 and smaller) are all "small launches" there (units * 16 < CUs * 32 * 24), so 32 or more samples
 select 32 in flight.  On the GPU the 32-in-flight forms, <32, *, 8> included, are reached through that rule.  The plans' other
 two ways to them (`big && nspp >= 128`, and the cached table of a launch that is not small) need frames of 12 288 work units or
-more, whose oracle renders do not fit a test; tests/test_launch_plan_cpu.py pins both by name on the benchmark's own frame."""
+more, whose oracle renders do not fit a test; tests/test_launch_plan_cpu.py pins both by name on the benchmark's own frame.
+
+The matrix's own tiling is regular: at tile sizes 32 and 16 the clipped column and row of its frames are 8 pixels wide and high, a
+whole number of every pixel block of the packet kernels (8x8 ... 1x1), so there a work unit lies wholly inside its tile or wholly
+outside.  The oracle's frame does not depend on the tiling, so every render / paths / wf / aov row runs again, against the same
+oracle frames, on the tile lists of tests/tile_geometries.py (tile sizes 13 and 1, and a partition into unaligned blocks), whose
+units are cut by their tiles: the lanes outside the tile inside a live unit, the slots' untouched remainder and the hand-out order
+are then held per instantiation (tiled_rows; tests/test_tile_geometries_cpu.py shows that every row keeps its name there and that
+units are in fact cut).  STAGED_BATCHES are the frames that take the staged pipeline through several tile batches."""
 
 DEFAULTS = {"packet_samples_in_flight": 0, "packet_mask_cache": 1, "packet_stack_registers": 64, "packet_rays_per_lane": 1, "paths_pooled": 1}
 # the frames of the matrix: render / path / staged cases 3 x 2 tiles with the right column and bottom row clipped; the feature planes'
@@ -73,6 +81,22 @@ def _row(api, scene, spp, also=(), **opts):
     o = {short[k]: v for k, v in opts.items()}
     trav = o.pop("traversal", "packets")
     return {"api": api, "scene": scene, "spp": spp, "opts": o, "traversal": trav, "also": tuple(also)}
+
+
+def wf_configurations():
+    """the staged rows by configuration: the thirteen rows share eight (scene, options); {first row's key: every key that shares it}"""
+    seen = {}
+    for key, row in CASES.items():
+        if row["api"] == "wf":
+            seen.setdefault((row["scene"], tuple(sorted(row["opts"].items()))), []).append(key)
+    return {keys[0]: keys for keys in seen.values()}
+
+
+def tiled_rows():
+    """the rows whose call takes a tile list (render / paths / aov, and one staged row per configuration): what
+    tests/test_gpu_dispatch_matrix.py runs again on every geometry of tests/tile_geometries.py"""
+    first = set(wf_configurations())
+    return [k for k, row in CASES.items() if row["api"] in ("render", "paths", "aov") or k in first]
 
 
 CASES = {}
@@ -179,4 +203,25 @@ RAGGED = {
     "paths": (_row("paths", "teapot", 70), [
         (40, "render_paths_kernel<8, false, false, true>"), (17, "render_paths_kernel<8, false, false>"), (6, "render_paths_kernel<4, false, false>"),
         (4, "render_paths_kernel<4, false, false>"), (2, "render_paths_kernel<2, false, false>"), (1, "render_paths_kernel<1, false, false>")]),
+}
+
+# ---- the staged pipeline over several tile batches and sample chunks (tile_geometries "ragged26": 26 tiles in 64 x 64 slots) -----
+# launch_render_paths_wavefront walks the tile list in batches of tb = 2^21 / (tile_size^2 * min(samples of the pass, 64)) tiles and
+# every batch in chunks of 64 samples; at 64 samples or more tb = 8: batches of 8, 8, 8 and 2 tiles, chunks 64 + 6 at 70 samples.
+# (scene, samples per pixel, the MP_FLAG_ACCUMULATE passes (one = a single launch), MP_FLAG_CHUNKED_SUM)
+def staged_names(scene):
+    """every kernel the staged pipeline launches for `scene` under the default options (the stack in registers)"""
+    return set(_wf(scene.startswith("group"), False, scene.endswith("+rgb"))[2])
+
+
+STAGED_TILES = 26
+STAGED_BATCHES = {
+    "teapot": ("teapot", 70, (70,), False),
+    "teapot+rgb": ("teapot+rgb", 70, (70,), False),
+    "group+rgb": ("group+rgb", 70, (70,), False),
+    "teapot, passes 40 + 30": ("teapot", 70, (40, 30), False),
+    "teapot+rgb, passes 40 + 30": ("teapot+rgb", 70, (40, 30), False),
+    # sample chunks 64 + 36, 64 + 64 + 29 and 43 per batch; the flush of the first 256-sample chunk of the sum falls inside the second
+    # pass (its last sample chunk); the {chunk sum, count, f64 total} slot is carried per tile across batches and passes
+    "teapot, chunked sum, passes 100 + 157 + 43": ("teapot", 300, (100, 157, 43), True),
 }

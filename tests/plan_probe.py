@@ -67,20 +67,23 @@ def name(out, field="kernel"):
     return lib().mp_plan_kernel_name(getattr(out, field)).decode()
 
 
-def row_input(row, passes=None):
-    """a row of dispatch_cases as the GPU matrix runs it: its frame, its options"""
+def row_input(row, passes=None, tiling=None):
+    """a row of dispatch_cases as the GPU matrix runs it: its frame, its options; tiling = (tile_size, tile count) of another
+    tile list over the same frame (tests/tile_geometries.py)"""
     o = {**dc.DEFAULTS, **row["opts"]}
     res, ts = (dc.AOV_RES, dc.AOV_TS) if row["api"] == "aov" else (dc.RES, dc.TS)
     n_tiles = -(-res[0] // ts) * -(-res[1] // ts)
+    if tiling is not None:
+        ts, n_tiles = tiling
     return launch(dc.scene_facts(row["scene"]), n_tiles, ts, row["spp"], passes, traversal=1 if row["traversal"] == "groups" else 0,
                   max_depth=dc.DEPTH if row["api"] in ("paths", "wf") else 0, samples=o["packet_samples_in_flight"], lanes=o["packet_rays_per_lane"],
                   cache=o["packet_mask_cache"], pooled=o["paths_pooled"], regs=o["packet_stack_registers"])
 
 
-def row_names(row, passes=None):
+def row_names(row, passes=None, tiling=None):
     """every kernel name the plans give for the row's call"""
     api = API[row["api"]]
-    out = plan(api, row_input(row, passes), dc.N_RAYS)
+    out = plan(api, row_input(row, passes, tiling), dc.N_RAYS)
     assert out.rc == 0, out.error
     if api == STAGED:
         return {name(out), name(out, "vertex"), name(out, "trace"), "wf_scan_kernel", "wf_scatter_kernel", "wf_accumulate_kernel"}

@@ -3,7 +3,12 @@ tests/test_dispatch_census_cpu.py).  Each case builds the smallest input that se
 public API, asserts that mp_ctx_last_kernels names exactly that instantiation, and compares the result bit for bit with the
 oracle's for the same input (never with another GPU run).  Then the gate cases -- the mask cache's guards must send a frame to the
 UNCACHED kernel for the right reason -- and frames rendered as ragged MP_FLAG_ACCUMULATE passes, whose kernels follow the samples
-of each pass."""
+of each pass.
+
+The matrix's own tiling never cuts a work unit (dispatch_cases' header), so every render / paths / wf / aov row, and the ragged
+passes, run once more per tile list of tests/tile_geometries.py, against the same oracle frames: the row's names, the frame bit for
+bit, and -- in a tile buffer pre-filled with a sentinel between sentinel guards -- not one word changed outside the blocks.  Last,
+the staged pipeline on 26 tiles in 64 x 64 slots (dispatch_cases.STAGED_BATCHES): several tile batches of several sample chunks."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +18,8 @@ import minipath_amd as mp
 from minipath_amd import _lib, scenes
 from tests import aov_model, meshes
 from tests import dispatch_cases as dc
+from tests import plan_probe as pp
+from tests import tile_geometries as tg
 from tests.conftest import TEAPOT
 
 pytestmark = pytest.mark.gpu
@@ -21,6 +28,8 @@ F = np.float32
 NO = 0xFFFFFFFF
 FMAX = np.finfo(np.float32).max
 SEED = 0x5EED
+SENTINEL = 0x5A5A5A5A  # as a float 1.5e16: no pixel of a frame; as an id no primitive of these scenes
+PAD = 4096
 RES, TS, AOV_RES, AOV_TS, DEPTH = dc.RES, dc.TS, dc.AOV_RES, dc.AOV_TS, dc.DEPTH  # the frames the CPU plan tests size the same rows with
 GREY = [(0.8, 0.0), (0.2, 2.5), (0.6, 0.0)]
 RGB = [{"albedo": (0.9, 0.85, 0.8), "albedo2": (0.1, 0.15, 0.7), "checker": 6.0}, ((0.7, 0.2, 0.3), (0.0, 0.0, 0.0)),
@@ -40,7 +49,7 @@ class World:
 
         assert torch.cuda.is_available(), "gpu tests need a GPU"
         self.oracle, self.ctx = oracle, mp.Context(0)
-        self._scenes, self._renders, self._facts = {}, {}, {}
+        self._scenes, self._renders, self._facts, self._planes = {}, {}, {}, {}
 
     def options(self, row=None):
         for k, v in {**dc.DEFAULTS, **(row["opts"] if row else {})}.items():
@@ -100,22 +109,37 @@ class World:
     def sampler(self, key, res):
         return self.oracle.sampler_from_array(self.scene(key)["cam"].build_sampler(res).as_array())
 
-    def expected(self, key, kind, res, spp):
-        """the oracle's frame: (f32, u8, ray segments or None); kind "render" or "paths"; cached"""
-        k = (key, kind, res, spp)
+    def expected(self, key, kind, res, spp, chunked=False):
+        """the oracle's frame: (f32, u8, ray segments or None); kind "render" or "paths"; cached.  The oracle renders with the
+        matrix's TS whatever tile list the GPU gets: its image does not depend on the tiling.  chunked: MP_FLAG_CHUNKED_SUM's rule"""
+        k = (key, kind, res, spp) + (("chunked",) if chunked else ())
         if k not in self._renders:
             s, smp = self.scene(key), self.sampler(key, res)
             if "sphere" in s:
-                assert kind == "render"
+                assert kind == "render" and not chunked
                 f, u8 = self.oracle.render_tile_sphere(*s["sphere"], smp, res[0], spp, SEED, 0, 0, res[0], res[1])
                 self._renders[k] = (f, u8, None)
             elif kind == "render":
+                assert not chunked
                 f, u8, *_ = s["orc"].render_image_mt(smp, res[0], res[1], spp, SEED, TS, 16)
                 self._renders[k] = (f, u8, None)
             else:
-                f, u8, _, seg = s["orc"].render_image_paths_mt(smp, res[0], res[1], spp, SEED, DEPTH, TS, 16)
+                self.oracle.lib().mpo_set_chunked_sum(1 if chunked else 0)
+                try:
+                    f, u8, _, seg = s["orc"].render_image_paths_mt(smp, res[0], res[1], spp, SEED, DEPTH, TS, 16)
+                finally:
+                    self.oracle.lib().mpo_set_chunked_sum(0)
                 self._renders[k] = (f, u8, seg)
         return self._renders[k]
+
+    def expected_planes(self, key, spp):
+        """the feature planes' model over the oracle for the whole AOV frame, image-major; cached per (scene, samples)"""
+        k = (key, spp)
+        if k not in self._planes:
+            s = self.scene(key)
+            self._planes[k] = aov_model.planes(self.oracle, s["orc"].intersect, self.sampler(key, AOV_RES), AOV_RES[0], spp, SEED,
+                                               (0, 0, AOV_RES[0], AOV_RES[1]), s["table"])
+        return self._planes[k]
 
     def view_facts(self, key, res):
         """what the first sample of every pixel sees, from the oracle: (hit mask, member index per pixel)"""
@@ -166,57 +190,139 @@ def _stack_in_lds(world, row):
         assert bound <= regs
 
 
-def _frame(world, row, expect, res=RES):
-    """render / paths / wf rows: one frame through FrameRenderer, the names reported, the frame against the oracle"""
-    import torch
+class GuardedTiles:
+    """a tile-major buffer [n, ts, ts, 4] (float32, or int32 for the "ids" plane) pre-filled with the sentinel, in the middle of a
+    larger tensor of sentinels: include/minipath_hip.h's "clipped tiles leave the rest untouched", for blocks anywhere in their slot"""
 
-    s = world.scene(row["scene"])
-    paths = row["api"] in ("paths", "wf")
-    st = mp.RenderSettings(TS, row["spp"], res, seed=SEED, traversal=row["traversal"], max_depth=DEPTH if paths else 0, wavefront=row["api"] == "wf")
-    of, ou8, oseg = world.expected(row["scene"], "paths" if paths else "render", res, row["spp"])
-    world.assert_not_vacuous(row["scene"], res, of)
-    if "sphere" not in s:
-        _stack_in_lds(world, row)
-    fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], st)
-    fr.render()
-    names = world.kernels()
-    img, img8 = fr.untile()
-    torch.cuda.synchronize()
+    def __init__(self, blocks, ts, ids=False):
+        import torch
+
+        self.blocks, self.ts, self.count = blocks, ts, len(blocks) * ts * ts * 4
+        self.whole = torch.full((PAD + self.count + PAD,), SENTINEL, dtype=torch.int32, device="cuda")
+        body = self.whole[PAD:PAD + self.count]
+        self.buf = (body if ids else body.view(torch.float32)).view(len(blocks), ts, ts, 4)
+        assert self.buf.data_ptr() == self.whole.data_ptr() + 4 * PAD and self.buf.data_ptr() % 16 == 0
+        self.own = tg.owned(blocks, ts)
+
+    def refill(self):
+        self.whole.fill_(SENTINEL)
+
+    def assert_rest_untouched(self, what=""):
+        """after a synchronize: every word of a slot outside its block's w x h still holds the sentinel, and so do the guards"""
+        raw = self.whole.cpu().numpy().view(np.uint32)
+        assert np.all(raw[:PAD] == SENTINEL) and np.all(raw[-PAD:] == SENTINEL), f"{what}: a guard was written"
+        body = raw[PAD:-PAD].reshape(len(self.blocks), self.ts, self.ts, 4)
+        changed = body[~self.own] != SENTINEL
+        assert not changed.any(), f"{what}: {int(changed.sum())} words changed outside the blocks, slots {np.unique(np.nonzero(changed)[0]).tolist()[:8]}"
+        assert (body[self.own] != SENTINEL).any(axis=-1).all(), f"{what}: a pixel of a block was not written"
+
+
+def _assert_names(names, expect):
     if isinstance(expect, set):
         assert set(names) == expect and len(names) == len(expect), names
     else:
         assert names == expect, names
-    got = img.cpu().numpy()
-    assert np.array_equal(bits(got), bits(of)), f"{int(np.sum(bits(got) != bits(of)))} f32 values differ"
-    assert np.array_equal(img8.cpu().numpy(), ou8)
-    seg = int(fr.segments.item())
-    if paths:
-        assert seg == oseg and seg > res[0] * res[1] * row["spp"], "paths bounce: more segments than camera rays"
-    else:
-        assert seg == res[0] * res[1] * row["spp"]
 
 
-def _aov(world, name, row):
+def _rebalanced(fr, staged=False):
+    """FrameRenderer.rebalance() after a launch on the "ragged" list: every tile was charged, and the order it installs -- the
+    most expensive first, where the list begins with a block of three pixels -- is not the identity.  The staged pipeline ignores
+    tile_order / d_tile_cost (include/minipath_hip.h): there nothing is charged and the frame must simply not change."""
+    n = len(fr.tiles)
+    cost = fr.tile_cost[:n].cpu().numpy().copy()
+    order = fr.rebalance()
+    assert sorted(order) == list(range(n))
+    if staged:
+        assert not cost.any()
+        return
+    assert np.all(cost > 0), f"tiles without a cost: {np.nonzero(cost == 0)[0].tolist()}"
+    assert order != list(range(n)), "the hand-out order must differ from the list's"
+
+
+def _frame(world, row, expect, res=RES, geometry="grid"):
+    """render / paths / wf rows: one frame through FrameRenderer over the tile list of `geometry`, into a sentinel-filled buffer
+    between guards: the names reported, the frame against the oracle, nothing written outside the blocks"""
+    import torch
+
+    s = world.scene(row["scene"])
+    paths = row["api"] in ("paths", "wf")
+    tile_size, blocks = tg.geometry(geometry, res, TS)
+    st = mp.RenderSettings(tile_size, row["spp"], res, seed=SEED, traversal=row["traversal"], max_depth=DEPTH if paths else 0,
+                           wavefront=row["api"] == "wf")
+    of, ou8, oseg = world.expected(row["scene"], "paths" if paths else "render", res, row["spp"])
+    world.assert_not_vacuous(row["scene"], res, of)
+    if "sphere" not in s:
+        _stack_in_lds(world, row)
+    g = GuardedTiles(blocks, tile_size)
+    fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], st, tiles=None if geometry == "grid" else blocks, tile_buf=g.buf)
+    assert fr.tiles == blocks and sum(t.area() for t in blocks) == res[0] * res[1]
+
+    def render_and_check(what):
+        fr.render()
+        names = world.kernels()
+        img, img8 = fr.untile()
+        torch.cuda.synchronize()
+        _assert_names(names, expect)
+        got = img.cpu().numpy()
+        assert np.array_equal(bits(got), bits(of)), f"{what}: {int(np.sum(bits(got) != bits(of)))} f32 values differ"
+        assert np.array_equal(img8.cpu().numpy(), ou8), what
+        seg = int(fr.segments.item())
+        if paths:
+            assert seg == oseg and seg > res[0] * res[1] * row["spp"], "paths bounce: more segments than camera rays"
+        else:
+            assert seg == sum(t.area() for t in blocks) * row["spp"]
+        g.assert_rest_untouched(what)
+
+    render_and_check(geometry)
+    if geometry == "ragged":  # the measured hand-out order, over units that are mostly outside their tile: the same bits
+        _rebalanced(fr, staged=row["api"] == "wf")
+        g.refill()
+        render_and_check("ragged, rebalanced")
+
+
+def _aov(world, name, row, geometry="grid"):
     import torch
 
     s = world.scene(row["scene"])
     _stack_in_lds(world, row)
-    want = aov_model.planes(world.oracle, s["orc"].intersect, world.sampler(row["scene"], AOV_RES), AOV_RES[0], row["spp"], SEED,
-                            (0, 0, AOV_RES[0], AOV_RES[1]), s["table"])
+    want = world.expected_planes(row["scene"], row["spp"])
     hits = want["ids"][..., 3]
     assert 0 < hits.sum() < hits.size, "the view must hold hits and misses"
     if s["group"]:
         assert len(np.unique(want["ids"][..., 1][hits == 1])) >= 2, "at least two members in view"
         assert len(np.unique(want["albedo"][..., :3].reshape(-1, 3)[hits.reshape(-1) == 1], axis=0)) >= 2, "at least two colours in view"
-    fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], mp.RenderSettings(AOV_TS, row["spp"], AOV_RES, seed=SEED))
-    out = fr.render_aov()
+    tile_size, blocks = tg.geometry(geometry, AOV_RES, AOV_TS)
+    fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], mp.RenderSettings(tile_size, row["spp"], AOV_RES, seed=SEED),
+                          tiles=None if geometry == "grid" else blocks)
+    assert fr.tiles == blocks
+
+    def same_as_model(planes, what):
+        img = {k: fr.untile_plane(v) for k, v in planes.items()}
+        torch.cuda.synchronize()
+        for k in ("shade", "normal", "albedo", "ids"):
+            got = img[k].cpu().numpy()
+            assert np.array_equal(bits(got), bits(want[k])), (what, k, int(np.sum(bits(got) != bits(want[k]))))
+
+    out = fr.render_aov()  # allocates its own planes: the names and the bits
     names = world.kernels()
-    img = {k: fr.untile_plane(v) for k, v in out.items()}
-    torch.cuda.synchronize()
     assert names == [name], names
-    for k in ("shade", "normal", "albedo", "ids"):
-        got = img[k].cpu().numpy()
-        assert np.array_equal(bits(got), bits(want[k])), (k, int(np.sum(bits(got) != bits(want[k]))))
+    same_as_model(out, geometry)
+    if geometry != "ragged":
+        return
+    # the same frame through render_aov_pass into sentinel-filled planes between guards, then once more in the measured order
+    guarded = {k: GuardedTiles(blocks, tile_size, ids=k == "ids") for k in ("shade", "normal", "albedo", "ids")}
+    planes = {k: v.buf for k, v in guarded.items()}
+    for what in ("ragged, one pass", "ragged, rebalanced"):
+        assert fr.render_aov_pass(planes) == row["spp"]
+        names = world.kernels()
+        assert names == [name], names
+        same_as_model(planes, what)
+        for k, v in guarded.items():
+            v.assert_rest_untouched(f"{what}, {k}")
+        if what == "ragged, one pass":
+            _rebalanced(fr)
+            for v in guarded.values():
+                v.refill()
 
 
 def _box_exit(info, o, d):
@@ -386,10 +492,7 @@ def test_mask_cache_gate(world, guard):
         world.options()
 
 
-@pytest.mark.parametrize("which", list(dc.RAGGED))
-def test_ragged_passes_select_by_the_pass(world, which):
-    """One frame of 70 samples per pixel as MP_FLAG_ACCUMULATE passes of falling size: every pass is launched on the kernel its own
-    sample count selects, and the finished frame is the oracle's single render."""
+def _ragged_passes(world, which, geometry="grid"):
     import torch
 
     row, passes = dc.RAGGED[which]
@@ -399,12 +502,18 @@ def test_ragged_passes_select_by_the_pass(world, which):
         s = world.scene(row["scene"])
         of, ou8, oseg = world.expected(row["scene"], row["api"], RES, row["spp"])
         world.assert_not_vacuous(row["scene"], RES)
-        fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], mp.RenderSettings(TS, row["spp"], RES, seed=SEED, max_depth=DEPTH if paths else 0))
+        tile_size, blocks = tg.geometry(geometry, RES, TS)
+        g = GuardedTiles(blocks, tile_size)
+        fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], mp.RenderSettings(tile_size, row["spp"], RES, seed=SEED, max_depth=DEPTH if paths else 0),
+                              tiles=None if geometry == "grid" else blocks, tile_buf=g.buf)
+        assert fr.tiles == blocks
         nxt, seen, seg = 0, [], 0
         for n, _ in passes:
             nxt = fr.render_pass(nxt, n)
             seen += world.kernels()
             seg += int(fr.segments.item())
+            # between passes: the running sums neither leak into the lanes outside a block nor come back from them
+            g.assert_rest_untouched(f"after sample {nxt}")
         assert nxt == row["spp"]
         assert seen == [k for _, k in passes], seen
         img, img8 = fr.untile()
@@ -415,3 +524,90 @@ def test_ragged_passes_select_by_the_pass(world, which):
             assert seg > RES[0] * RES[1] * row["spp"]
     finally:
         world.options()
+
+
+@pytest.mark.parametrize("which", list(dc.RAGGED))
+def test_ragged_passes_select_by_the_pass(world, which):
+    """One frame of 70 samples per pixel as MP_FLAG_ACCUMULATE passes of falling size: every pass is launched on the kernel its own
+    sample count selects, and the finished frame is the oracle's single render."""
+    _ragged_passes(world, which)
+
+
+# ---- the same rows on tile lists that cut their pixel blocks ---------------------------------------------------------------------
+@pytest.mark.parametrize("geometry", tg.GEOMETRIES)
+@pytest.mark.parametrize("name", dc.tiled_rows())
+def test_instantiation_on_cut_tiles(world, name, geometry):
+    """Every render / paths / aov row and every configuration of the staged rows on tile_size 13, on one tile per pixel and on a
+    partition into unaligned blocks (tests/tile_geometries.py; tests/test_tile_geometries_cpu.py shows that units are cut there and
+    that the plans keep the row's names): the names, the oracle's frame bit for bit, the segments, and not one word of the
+    sentinel-filled tile buffer changed outside the blocks; on the unaligned blocks once more in the hand-out order
+    FrameRenderer.rebalance() measures."""
+    row = dc.CASES[name]
+    world.options(row)
+    try:
+        if row["api"] in ("render", "paths"):
+            _frame(world, row, [name], geometry=geometry)
+        elif row["api"] == "wf":
+            _frame(world, row, {name, *row["also"]}, geometry=geometry)
+        else:
+            _aov(world, name, row, geometry=geometry)
+    finally:
+        world.options()
+
+
+@pytest.mark.parametrize("geometry", ["grid13", "ragged"])
+@pytest.mark.parametrize("which", list(dc.RAGGED))
+def test_ragged_passes_on_cut_tiles(world, which, geometry):
+    """The ragged MP_FLAG_ACCUMULATE passes over cut units: the kernels per pass, the oracle's frame, and between the passes the
+    part of every slot that its block does not own still holds the sentinel."""
+    _ragged_passes(world, which, geometry)
+
+
+# ---- the staged pipeline over several tile batches and sample chunks -------------------------------------------------------------
+@pytest.mark.parametrize("case", list(dc.STAGED_BATCHES))
+def test_staged_pipeline_over_tile_batches(world, case):
+    """26 tiles in 64 x 64 slots at 64 samples or more per pass: launch_render_paths_wavefront walks them in batches of 8, 8, 8 and
+    2 (tests/test_tile_geometries_cpu.py holds that from the plan), each batch in sample chunks 64 + 6 -- tile_base > 0, the
+    output slot tile_base + tile_l, the resets between batches, a shorter last batch, carry_in / finalize across batches and,
+    with passes, the state an earlier pass left in the later batches' slots.  Against the oracle, and against the fused kernel."""
+    import torch
+
+    scene, spp, passes, chunked = dc.STAGED_BATCHES[case]
+    world.options()
+    s = world.scene(scene)
+    tile_size, blocks = tg.geometry("ragged26", RES, TS)
+    facts = dc.scene_facts(scene)
+    plan = pp.plan(pp.STAGED, pp.launch(facts, len(blocks), tile_size, spp, max_depth=DEPTH, chunked=1 if chunked else 0))
+    assert plan.rc == 0 and plan.tb < len(blocks) and plan.ws_bytes < 256 << 20, "the workspace of a batch: 192 MB today"
+    of, ou8, oseg = world.expected(scene, "paths", RES, spp, chunked=chunked)
+    world.assert_not_vacuous(scene, RES, of)
+    staged_names = dc.staged_names(scene)
+    results = {}
+    for wavefront in (True, False):
+        st = mp.RenderSettings(tile_size, spp, RES, seed=SEED, max_depth=DEPTH, wavefront=wavefront, chunked_sum=chunked)
+        g = GuardedTiles(blocks, tile_size)
+        fr = mp.FrameRenderer(mp.Scene(s["gpu"]), s["cam"], st, tiles=blocks, tile_buf=g.buf)
+        nxt, seg = 0, 0
+        for n in passes:
+            if len(passes) == 1:  # one launch, without MP_FLAG_ACCUMULATE
+                fr.render()
+                nxt = spp
+            else:
+                nxt = fr.render_pass(nxt, n)
+            names = world.kernels()
+            seg += int(fr.segments.item())
+            if wavefront:
+                assert set(names) == staged_names and len(names) == len(staged_names), names
+            else:
+                assert len(names) == 1 and names[0].startswith("render_paths_"), names
+            g.assert_rest_untouched(f"{'staged' if wavefront else 'fused'}, after sample {nxt}")
+        assert nxt == spp
+        img, img8 = fr.untile()
+        torch.cuda.synchronize()
+        results[wavefront] = (img.cpu().numpy(), img8.cpu().numpy(), seg, g.buf.cpu().numpy())
+    for wavefront, (img, img8, seg, _) in results.items():
+        what = "staged" if wavefront else "fused"
+        assert np.array_equal(bits(img), bits(of)), f"{what}: {int(np.sum(bits(img) != bits(of)))} f32 values differ"
+        assert np.array_equal(img8, ou8), what
+        assert seg == oseg and seg > RES[0] * RES[1] * spp, what
+    assert np.array_equal(bits(results[True][3]), bits(results[False][3])), "the staged and the fused tile buffers"
