@@ -13,9 +13,10 @@ from .renderer import (RenderProgress, RenderProgressSnapshot, RenderSettings, r
 from .denoise import AtrousDenoiser  # noqa: F401  (denoise/libminipath_denoise.so is loaded on first use, not here)
 from .adaptive import AdaptiveSampler  # noqa: F401  (adaptive/libminipath_adaptive.so is loaded on first use, not here)
 from .temporal import TemporalAccumulator  # noqa: F401  (temporal/libminipath_temporal.so is loaded on first use, not here)
+from .secondary import SecondaryVisibility  # noqa: F401  (secondary/libminipath_secondary.so is loaded on first use, not here)
 
 __all__ = [
     "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
-    "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "Sphere", "TemporalAccumulator", "TriangleBvh", "render", "render_tile",
+    "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "SecondaryVisibility", "Sphere", "TemporalAccumulator", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]
