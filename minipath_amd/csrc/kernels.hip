@@ -31,7 +31,7 @@
 #ifdef MP_PROF_MISSES  // profiling builds only (tools/build_variant.sh): slow-path calls of the mask cache, read by mp_prof_read
 namespace mp {
 namespace {
-__device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask builds [2] inner links followed [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk
+__device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask builds [2] inner links followed [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk [7] pops skipped on an empty-mask leaf
 }  // namespace
 }  // namespace mp
 #define MP_PROF_COUNT(i) do { if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_prof[i], 1ull); } while (0)
@@ -565,6 +565,16 @@ __device__ __forceinline__ bool trace_packet_cached(const DevScene& sc, const Ra
         }
         cur -= 1u;  // last entry first
         const uint32_t src = __builtin_amdgcn_readfirstlane(mcache[(cur >> 16) + (cur & 0xFFFFu)]);
+#ifndef MP_NO_EMPTY_SKIP
+        // An entry with kEmptyLeafBit set is a leaf whose unit triangle mask is empty (marked below by the visit that found it so):
+        // a visit would test no triangle and change no ray's state, so the record load and the slab test are skipped too.  The mask
+        // depends on the leaf and the unit's bounds alone, and whatever changes the bounds or resets the arena rebuilds the lists,
+        // unmarked, before they are walked again.  Record indices are below 2^28 (2^24 nodes x 16 slots, checked at upload).
+        if (static_cast<int32_t>(src) < 0) {
+            MP_PROF_COUNT(7);
+            continue;
+        }
+#endif
         const bool pon = __builtin_amdgcn_inverse_ballot_w64(pm);
         // (base + a 32-bit byte offset: s_load's register-offset form; fewer than 2^24 nodes, checked at upload)
         const krec8 rec = *reinterpret_cast<const __attribute__((address_space(4))) krec8*>(reinterpret_cast<const __attribute__((address_space(4))) char*>(nodes) + scalar_u(src * 32u));
@@ -604,23 +614,23 @@ __device__ __forceinline__ bool trace_packet_cached(const DevScene& sc, const Ra
             // intersect_triangles :104-140 ; every lane walks the leaf's surviving triangles in (packet, lane) order with a strict `<`
             const uint32_t first = link >> 6, n_real = link & 63u;
             kfp tp = tris + static_cast<size_t>(first) * (8 * kTriDwords);
+            static_assert(kExitTiny == kTiny && kExitHuge == kHuge, "mask_cache.h's copies of the early-out constants");
             const float thr = lim >= 0.0f ? -kTiny : INFINITY;  // early-out threshold: a disabled ray is always "surely rejected"
             auto test = [&](const float v0x, const float v0y, const float v0z, const float e1x, const float e1y, const float e1z,
                             const float e2x, const float e2y, const float e2z, const uint32_t tri) {
-                // triangle.rs:183-217 (early-out argument: see trace_packet_impl)
+                // triangle.rs:183-217
                 const float hx = fms(r.dy, e2z, r.dz * e2y), hy = fms(r.dz, e2x, r.dx * e2z), hz = fms(r.dx, e2y, r.dy * e2x);
                 const float det = fma_dot(e1x, e1y, e1z, hx, hy, hz);
                 const float sx = r.ox - v0x, sy = r.oy - v0y, sz = r.oz - v0z;
                 const float un = fma_dot(sx, sy, sz, hx, hy, hz);
-                const uint32_t det_sign = as_u(det) & 0x80000000u;
-                const bool det_ok = fabsf(det) <= kHuge;
-                const float xu = det_ok ? as_f(as_u(un) ^ det_sign) : 1.0f;
-                if (__ballot(!(xu <= thr)) == 0) return;  // no live ray can have u >= 0
+                // the two early-outs, near side and far side (mask_cache.h: tri_exit1_key, tri_exit2_key and their proof)
+                const float xu = tri_flipped(det, un);
+                if (__ballot(!(tri_exit1_key(det, xu) <= thr)) == 0) return;  // no live ray can have 0 <= u <= 1
                 const float qx = fms(sy, e1z, sz * e1y), qy = fms(sz, e1x, sx * e1z), qz = fms(sx, e1y, sy * e1x);
                 const float vn = fma_dot(r.dx, r.dy, r.dz, qx, qy, qz);
                 const float tn = fma_dot(e2x, e2y, e2z, qx, qy, qz);
-                const float xv = det_ok ? as_f(as_u(vn) ^ det_sign) : 1.0f, xt = det_ok ? as_f(as_u(tn) ^ det_sign) : 1.0f;
-                if (__ballot(!(fminf(fminf(xu, xv), xt) <= thr)) == 0) return;
+                const float xv = tri_flipped(det, vn), xt = tri_flipped(det, tn);
+                if (__ballot(!(tri_exit2_key(det, xu, xv, xt) <= thr)) == 0) return;  // ... nor u, v, t >= 0 with u + v <= 1
                 // inv_det = 1 / det (:201) through rm::rcp_short when every lane's |det| lies in its window [2^-94, 2^125] (ray_math.h:
                 // there the short sequence is the IEEE division's own, minus range fix-ups that do nothing, so inv_det is the same
                 // number); otherwise the whole wave divides.  Only live rays need the window (the others cannot accept: t < lim < 0
@@ -655,6 +665,14 @@ __device__ __forceinline__ bool trace_packet_cached(const DevScene& sc, const Ra
             }
             // the next survivor's record is fetched while this one is tested (one register set rotated through moves: a two-set
             // form without the moves measured 3 % slower -- code size; no prefetch at all: the same time)
+#ifndef MP_NO_EMPTY_SKIP
+            if (todo == 0 && (cur >> 16) != static_cast<uint32_t>(kRootListSlot)) {
+                // nothing to test here for any ray inside the unit's bounds: mark the list entry this leaf was popped from, so that
+                // the unit's later pops of it stop at the entry (above).  The root's own slot is rewritten by every pass: not marked.
+                if ((threadIdx.x & 63u) == 0u) mcache[(cur >> 16) + (cur & 0xFFFFu)] = src | kEmptyLeafBit;
+                wave_lds_sync();
+            }
+#endif
             if (todo != 0) {
                 uint32_t c = static_cast<uint32_t>(__builtin_ctzll(todo));
                 todo &= ~(1ull << c);

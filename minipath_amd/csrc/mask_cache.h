@@ -2,7 +2,7 @@
 // prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
 // that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
 // per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define
-// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES / MP_ARENA_ENTRIES / MP_NODE_SLOT_MASK before including it.
+// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES / MP_ARENA_ENTRIES / MP_NODE_SLOT_MASK / MP_NO_FAR_EXIT before including it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -360,7 +360,8 @@ __device__ __forceinline__ bool bounds_may_hit(const float* b, const float bmn[3
 // cache).  Absorbing stops where the space left could not hold the entries still pending, each taken as one unexpanded entry.
 constexpr uint32_t kNullLink = 0xFFFFFFF8u;      // MP_LINK_NULL
 constexpr uint32_t kListOverflow = 0xFFFFFFFFu;  // unit_list_build: the list did not fit, table and arena were reset
-constexpr int kListDepth = 64;                   // continuation stack of the depth-first pass (lane registers)
+constexpr uint32_t kEmptyLeafBit = 0x80000000u;  // set by the WALK in an arena entry (never by the builder): a leaf whose unit triangle mask is empty
+constexpr int kListDepth = 64;                  // continuation stack of the depth-first pass (lane registers)
 __device__ __forceinline__ uint32_t node_slot(uint32_t node) {
     return min(node & static_cast<uint32_t>(kMaskCacheEntries - 1) & MP_NODE_SLOT_MASK, static_cast<uint32_t>(kMaskCacheEntries - 2));
 }
@@ -510,6 +511,58 @@ __device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3]
     const Iv t = iv_mul(inv, iv_fma_c(q[2], e2[2], iv_fma_c(q[1], e2[1], iv_mul_c(q[0], e2[0]))));
     const bool miss = u.hi < 0.0f || v.hi < 0.0f || (u.lo + v.lo) > 1.0f || t.hi < 0.0f;
     return !miss;
+}
+
+// ---- the per-ray early-outs of a triangle test: "surely rejected" before the division ------------------------------------------------
+// The walk computes det, then the numerators un, vn, tn of u = fl(inv_det * un), v, t (triangle.rs:183-217, inv_det = fl(1 / det):
+// correctly rounded; rm::rcp_short is the same number) and accepts a ray iff u >= 0, v >= 0, fl(u + v) <= 1, t >= 0, t < limit.
+// A wave leaves a triangle after un (stage 1) or after vn and tn (stage 2) when EVERY lane is surely rejected; a lane is surely
+// rejected when its key is <= its threshold `thr`: -2^-40 for a live ray, +inf for a disabled one (always rejected).  The keys are
+// minNum chains, so a NaN operand drops out and an all-NaN key compares false: NaN never rejects.
+//   x = tri_flipped(det, num): the numerator with det's sign flipped in, or +1 where |det| > 2^40 or det is NaN (no verdict there).
+// NEAR side (x <= -2^-40): num's sign differs from det's, |num| >= 2^-40 and |det| <= 2^40, so the quotient fl(fl(1/det) * num) is a
+//   non-zero negative number (|quotient| >= 2^-80 (1 - eps): no underflow to -0, which would pass `>= 0`); det = +-0 or a denormal
+//   with an infinite reciprocal gives -inf.  u >= 0 (v >= 0, t >= 0) fails.
+// FAR side: f(x) = fl(|det| * (1 + 2^-20) - x), ONE rounding (fma).  f(x) <= -2^-40 means the exact difference is negative (a
+//   non-negative real never rounds below zero): x > |det| (1 + 2^-20) =: A.  (The rule is x > A; demanding 2^-40 of the difference
+//   lets the far side share the near side's threshold, hence its compare, and gives up only numerators within 2^-40 of A.)
+//   * f(xu) <= -2^-40.  |det| is not above 2^40 here (x would be 1 and f positive or NaN).  If inv_det is finite, u = xu / |det|
+//     (1 + d1)(1 + d2) with |d| <= 2^-24 (u is above 1: no underflow; an overflow gives +inf), so u > (1 + 2^-20)(1 - 2^-24)^2 >
+//     1 + 2^-21.  If inv_det is infinite (det = +-0 or a small denormal), xu > 0 makes u = +inf.  Then v < 0 is rejected; v NaN
+//     makes u + v NaN, and `<= 1` is false; v >= 0 gives fl(u + v) >= u > 1 (rounding is monotone).  The acceptance fails.
+//   * f(fl(xu + xv)) <= -2^-40.  If the computed u or v is negative or NaN the acceptance fails by itself.  Otherwise each is the
+//     rounded quotient of a numerator that is non-negative or so small that the quotient underflowed to -0 (it is then above
+//     -2^-149 |det|); with xu + xv >= fl(xu + xv)(1 - 2^-24) > A (1 - 2^-24): u + v >= (xu + xv) / |det| (1 - 2^-24)^2 - 2^-148 >
+//     (1 + 2^-20)(1 - 2^-24)^3 - 2^-148 > 1 + 2^-21, and its rounding is above 1.  With an infinite inv_det one of u, v is +inf
+//     (the positive numerator's) and the sum is +inf or NaN.  The acceptance fails.
+//   * |det| > 2^40 or NaN: x = 1 for every numerator, f = fl(|det| (1 + 2^-20) - 1 or - 2) is positive, +inf or NaN: never rejects,
+//     as on the near side.
+// Disabled lanes: thr = +inf, and every key that is not NaN is <= +inf; a NaN key (a disabled lane's garbage) keeps the wave at the
+// triangle, which costs time and decides nothing -- as before.
+// Counted (tools/tri_exit_count.py, profiles/tri_exits_notes.md): of the 8.3 triangles per pass of the metric's frame that reach the
+// division, 3.6 are accepted by no ray, all of them on the far side; the far keys take them out at stage 1 or 2.
+// -DMP_NO_FAR_EXIT: the near side alone (A/B builds, tools/build_variant.sh).
+constexpr float kExitTiny = 9.094947017729282e-13f;  // 2^-40
+constexpr float kExitHuge = 1099511627776.0f;        // 2^40
+constexpr float kFarSlack = 1.00000095367431640625f; // 1 + 2^-20
+__device__ __forceinline__ float tri_flipped(float det, float num) {
+    return fabsf(det) <= kExitHuge ? as_f(as_u(num) ^ (as_u(det) & 0x80000000u)) : 1.0f;
+}
+__device__ __forceinline__ float tri_far_key(float det, float x) { return __builtin_fmaf(fabsf(det), kFarSlack, -x); }
+__device__ __forceinline__ float tri_exit1_key(float det, float xu) {
+#ifdef MP_NO_FAR_EXIT
+    return xu;
+#else
+    return fminf(xu, tri_far_key(det, xu));
+#endif
+}
+__device__ __forceinline__ float tri_exit2_key(float det, float xu, float xv, float xt) {
+    const float near_key = fminf(fminf(xu, xv), xt);
+#ifdef MP_NO_FAR_EXIT
+    return near_key;
+#else
+    return fminf(fminf(near_key, tri_far_key(det, xu)), tri_far_key(det, xu + xv));
+#endif
 }
 
 }  // namespace mc

@@ -2,6 +2,8 @@
 // (tests/test_mask_cache_gpu.py), built with the library's flags.  Each entry point generates its cases on the device from a seed
 // and a counter-based hash and checks the predicate that the walk inlines against the walk's own per-ray arithmetic:
 //   * tri_may_hit against the per-ray Moeller-Trumbore sequence (triangle.rs:183-217, `1.0f / det`) of 192 rays inside B;
+//   * tri_exit1_key / tri_exit2_key (the walk's early-outs of a triangle test, as a wave decides them) against the same per-ray
+//     sequence of 64 rays inside B (tests/test_tri_exits_gpu.py);
 //   * bounds_may_hit<OCT> against slab<false, OCT> (aabb.rs:254-284, limit FLT_MAX) of 192 rays inside B, all eight patterns;
 //   * mask_cache_ray_ok against its plain definition, every f32 bit pattern in each of the nine components;
 //   * bounds_deviation against `v < lo || v > hi`;
@@ -255,6 +257,49 @@ __global__ void tri_kernel(uint64_t seed, uint64_t base, uint64_t ncases, unsign
         rec[35] = keep ? 1u : 0u;
     }
     record_case(out, !keep && any, c, any, !keep, any_edge && !any_inner);
+}
+
+// ---- (a') the early-outs of a triangle test: tri_exit1_key / tri_exit2_key --------------------------------------------------------
+// One wave per case of gen_tri_case: 64 rays inside its box (corners, inward corners or interior points, by the case index), a
+// random set of them live (one case in eight: all).  The wave-level decision of the walk -- leave the triangle at stage 1 or 2 when
+// every lane's key is <= its threshold (-2^-40 live, +inf disabled) -- against the plain per-ray sequence (mt_ray, `1.0f / det`) of
+// the live rays.  Counters: [0] cases the wave leaves although a live ray hits, [3] cases some live ray hits, [4] cases left at
+// stage 1, [5] cases left at stage 2 only, [6] cases left that the near side alone (a numerator surely negative) would not leave.
+__global__ void exit_kernel(uint64_t seed, uint64_t base, uint64_t ncases, unsigned long long* out, uint32_t*) {
+    const uint64_t c = base + (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (c >= ncases) return;  // (whole waves)
+    float b[20], v0[3], v1[3], v2[3];
+    gen_tri_case(seed, c, b, v0, v1, v2);
+    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    float lo[6], hi[6];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { lo[k] = b[k]; hi[k] = b[3 + k]; lo[3 + k] = b[13 + k]; hi[3 + k] = b[16 + k]; }
+    float x[6];
+    case_ray(lo, hi, static_cast<uint32_t>(c % 3u) * 64u + lane, seed, c, x);
+    const uint64_t hl = hsh(seed, c, 90);
+    const uint64_t live_mask = (hl & 7u) == 0u ? ~0ull : (hsh(seed, c, 91) | (1ull << (hl >> 58)));
+    const bool live = ((live_mask >> lane) & 1u) != 0u;
+    // the walk's sequence up to the division (kernels.hip, trace_packet_cached)
+    const float dx = x[3], dy = x[4], dz = x[5];
+    const float hx = fms(dy, e2[2], dz * e2[1]), hy = fms(dz, e2[0], dx * e2[2]), hz = fms(dx, e2[1], dy * e2[0]);
+    const float det = fma_dot(e1[0], e1[1], e1[2], hx, hy, hz);
+    const float sx = x[0] - v0[0], sy = x[1] - v0[1], sz = x[2] - v0[2];
+    const float un = fma_dot(sx, sy, sz, hx, hy, hz);
+    const float thr = live ? -kExitTiny : INFINITY;
+    const float xu = tri_flipped(det, un);
+    const bool exit1 = __ballot(!(tri_exit1_key(det, xu) <= thr)) == 0;
+    const float qx = fms(sy, e1[2], sz * e1[1]), qy = fms(sz, e1[0], sx * e1[2]), qz = fms(sx, e1[1], sy * e1[0]);
+    const float vn = fma_dot(dx, dy, dz, qx, qy, qz);
+    const float tn = fma_dot(e2[0], e2[1], e2[2], qx, qy, qz);
+    const float xv = tri_flipped(det, vn), xt = tri_flipped(det, tn);
+    const bool exit2 = __ballot(!(tri_exit2_key(det, xu, xv, xt) <= thr)) == 0;
+    const bool near1 = __ballot(!(xu <= thr)) == 0, near2 = __ballot(!(fminf(fminf(xu, xv), xt) <= thr)) == 0;
+    const TriRay tr = mt_ray(x, v0, e1, e2);
+    const bool any = __ballot(live && tr.hit) != 0;
+    const bool left = exit1 || exit2;
+    record_case(out, left && any, c, any, exit1, exit2 && !exit1);
+    if (lane == 0u && left && !(near1 || near2)) atomicAdd(out + 6, 1ull);
 }
 
 // ---- (b) bounds_may_hit<OCT> -------------------------------------------------------------------------------------------------------
@@ -717,6 +762,8 @@ int run_cases(K kernel, uint64_t seed, uint64_t ncases, uint32_t* dump_dev, unsi
 extern "C" {
 // (a) tri_may_hit: ncases cases
 int mp_mask_probe_tri(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(tri_kernel, seed, ncases, nullptr, out); }
+// (a') tri_exit1_key / tri_exit2_key, the wave's decision: ncases cases
+int mp_mask_probe_exits(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(exit_kernel, seed, ncases, nullptr, out); }
 // (b) bounds_may_hit<OCT>: ncases cases, case c of pattern c & 7
 int mp_mask_probe_box(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(box_kernel, seed, ncases, nullptr, out); }
 // (a) / (b) with a dump of every case to `host` (ncases * mp_mask_probe_dump_dwords() dwords): kind 0 triangles, 1 boxes

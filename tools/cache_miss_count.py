@@ -29,3 +29,4 @@ passes = units * (spp // S)
 print(f"{which} x{spp}: per unit: node-list slow paths {out[0] / units:.1f}, leaf-mask slow paths {out[1] / units:.1f}, bounds (re)set {out[3] / units:.2f};"
       f" per pass: node visits (inner links followed) {out[2] / passes:.2f}")
 print(f"{which} x{spp}: per unit: node-table evictions {out[4] / units:.3f}, arena resets {out[5] / units:.4f}; passes left to the uncached walk: {out[6]} of {passes}")
+print(f"{which} x{spp}: per pass: pops skipped on an empty-mask leaf {out[7] / passes:.3f}")
