@@ -14,9 +14,10 @@ from .denoise import AtrousDenoiser  # noqa: F401  (denoise/libminipath_denoise.
 from .adaptive import AdaptiveSampler  # noqa: F401  (adaptive/libminipath_adaptive.so is loaded on first use, not here)
 from .temporal import TemporalAccumulator  # noqa: F401  (temporal/libminipath_temporal.so is loaded on first use, not here)
 from .secondary import SecondaryVisibility  # noqa: F401  (secondary/libminipath_secondary.so is loaded on first use, not here)
+from .resample import GuidedResampler  # noqa: F401  (resample/libminipath_resample.so is loaded on first use, not here)
 
 __all__ = [
-    "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
+    "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "GuidedResampler", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
     "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "SecondaryVisibility", "Sphere", "TemporalAccumulator", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]
