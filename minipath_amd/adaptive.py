@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _postlib
 from ._lib import MP_OK, MinipathError
 from .renderer import FrameRenderer
 
@@ -37,18 +37,7 @@ def lib() -> C.CDLL:
     """Load libminipath_adaptive.so.  Fails loudly when it has not been built."""
     global _lib_handle
     if _lib_handle is None:
-        if not os.path.exists(ADAPTIVE_SO_PATH):
-            raise ImportError(f"{ADAPTIVE_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- adaptive sampling has no CPU fallback")
-        try:
-            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
-        except ImportError:
-            pass
-        L = C.CDLL(ADAPTIVE_SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib_handle = L
+        _lib_handle = _postlib.load(ADAPTIVE_SO_PATH, SIGNATURES, "adaptive sampling has no CPU fallback")
     return _lib_handle
 
 
@@ -60,11 +49,7 @@ def check(rc: int) -> None:
 
 def last_kernels() -> list:
     """mpa_last_kernels: the kernel of the calling thread's last launching call."""
-    need = C.c_size_t()
-    check(lib().mpa_last_kernels(None, 0, C.byref(need)))
-    buf = C.create_string_buffer(need.value + 1)
-    check(lib().mpa_last_kernels(buf, need.value + 1, None))
-    return [n for n in buf.value.decode().split("\n") if n]
+    return _postlib.last_kernels(lib().mpa_last_kernels, check)
 
 
 def round_bounds(sample_count: int, min_samples: int, round_samples: int) -> list:
@@ -149,9 +134,7 @@ class AdaptiveSampler:
 
     # ---- the three device operations on this sampler's planes -------------------------------------------------------------------
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _postlib.stream_of(self.device)
 
     def _move(self, n, src, src_idx, dst, dst_idx):
         check(lib().mpa_move_tiles(self.device_id, int(self.settings.tile_size), n, src.data_ptr(), src.shape[0],

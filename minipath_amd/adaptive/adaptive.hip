@@ -6,11 +6,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "../../include/minipath_adaptive.h"
+#include "../post/post_abi.h"
 
 namespace mpa {
 
@@ -144,51 +142,7 @@ __global__ __launch_bounds__(BLOCK) void finish_tiles_kernel(float4* __restrict_
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-static thread_local std::string g_last_kernels;
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(MP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// No exception crosses the C ABI: every extern "C" body runs inside guarded().
-template <class F>
-int guarded(F&& body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        try { g_last_error = "out of host memory (std::bad_alloc)"; } catch (...) {}
-        return MP_ERR_NOMEM;
-    } catch (const std::exception& ex) {
-        try { g_last_error = std::string("unexpected exception: ") + ex.what(); } catch (...) {}
-        return MP_ERR_INVALID;
-    } catch (...) {
-        try { g_last_error = "unexpected exception"; } catch (...) {}
-        return MP_ERR_INVALID;
-    }
-}
-
-// The record of mpa_last_kernels: a call notes its kernel before it launches it.
-void note_kernel(const char* name) {
-    try { g_last_kernels = name; } catch (...) {}
-}
-
-// The calling thread's device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 constexpr uint64_t kMaxBlocks = 0x7FFFFFFFull;  // a grid is one dimension of at most 2^31 - 1 blocks
 
@@ -202,16 +156,7 @@ extern "C" {
 const char* mpa_last_error(void) { return g_last_error.c_str(); }
 
 int mpa_last_kernels(char* buf, size_t cap, size_t* needed) {
-    return guarded([&]() -> int {
-        if (cap && !buf) return fail(MP_ERR_INVALID, "NULL argument");
-        if (needed) *needed = g_last_kernels.size();
-        if (cap) {
-            const size_t n = std::min(cap - 1, g_last_kernels.size());
-            std::memcpy(buf, g_last_kernels.data(), n);
-            buf[n] = 0;
-        }
-        return MP_OK;
-    });
+    return guarded([&]() -> int { return copy_last_kernels(buf, cap, needed); });
 }
 
 int mpa_tile_error(int device_id, uint32_t tile_size, uint32_t n_slots, uint32_t samples_done, float threshold, float floor,
@@ -233,12 +178,10 @@ int mpa_tile_error(int device_id, uint32_t tile_size, uint32_t n_slots, uint32_t
 
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        note_kernel("tile_error_kernel");
-        hipLaunchKernelGGL(tile_error_kernel, dim3(n_slots), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                           reinterpret_cast<const float4*>(d_shade), reinterpret_cast<const float4*>(d_shade_sq),
-                           reinterpret_cast<const uint2*>(d_tile_wh), tile_size, r, threshold, floor, d_open, d_max_err);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "tile_error_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return launch(log, "tile_error_kernel", tile_error_kernel, dim3(n_slots), dim3(BLOCK), stream,
+                      reinterpret_cast<const float4*>(d_shade), reinterpret_cast<const float4*>(d_shade_sq),
+                      reinterpret_cast<const uint2*>(d_tile_wh), tile_size, r, threshold, floor, d_open, d_max_err);
     });
 }
 
@@ -257,12 +200,10 @@ int mpa_move_tiles(int device_id, uint32_t tile_size, uint32_t n, const void* d_
 
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        note_kernel("move_tiles_kernel");
-        hipLaunchKernelGGL(move_tiles_kernel, dim3(static_cast<uint32_t>(chunks * n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
-                           static_cast<const uint4*>(d_src), src_slots, d_src_slot, static_cast<uint4*>(d_dst), dst_slots, d_dst_slot,
-                           per_tile, static_cast<uint32_t>(chunks));
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "move_tiles_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return launch(log, "move_tiles_kernel", move_tiles_kernel, dim3(static_cast<uint32_t>(chunks * n)), dim3(BLOCK), stream,
+                      static_cast<const uint4*>(d_src), src_slots, d_src_slot, static_cast<uint4*>(d_dst), dst_slots, d_dst_slot,
+                      per_tile, static_cast<uint32_t>(chunks));
     });
 }
 
@@ -281,12 +222,10 @@ int mpa_finish_tiles(int device_id, uint32_t tile_size, uint32_t n_slots, uint32
 
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        note_kernel("finish_tiles_kernel");
-        hipLaunchKernelGGL(finish_tiles_kernel, dim3(static_cast<uint32_t>(chunks * n_slots)), dim3(BLOCK), 0,
-                           static_cast<hipStream_t>(stream), reinterpret_cast<float4*>(d_plane), d_samples,
-                           reinterpret_cast<const uint2*>(d_tile_wh), sample_count, tile_size, per_tile, static_cast<uint32_t>(chunks));
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "finish_tiles_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return launch(log, "finish_tiles_kernel", finish_tiles_kernel, dim3(static_cast<uint32_t>(chunks * n_slots)), dim3(BLOCK),
+                      stream, reinterpret_cast<float4*>(d_plane), d_samples, reinterpret_cast<const uint2*>(d_tile_wh), sample_count,
+                      tile_size, per_tile, static_cast<uint32_t>(chunks));
     });
 }
 

@@ -9,6 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from . import _postlib
 from ._lib import MP_OK, MinipathError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,18 +44,7 @@ def lib() -> C.CDLL:
     """Load libminipath_denoise.so.  Fails loudly when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(DENOISE_SO_PATH):
-            raise ImportError(f"{DENOISE_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- the denoiser has no CPU fallback")
-        try:
-            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
-        except ImportError:
-            pass
-        L = C.CDLL(DENOISE_SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _postlib.load(DENOISE_SO_PATH, SIGNATURES, "the denoiser has no CPU fallback")
     return _lib
 
 
@@ -66,11 +56,7 @@ def check(rc: int) -> None:
 
 def last_kernels() -> list:
     """mpd_last_kernels: the kernels of the calling thread's last launching call, distinct names in launch order."""
-    need = C.c_size_t()
-    check(lib().mpd_last_kernels(None, 0, C.byref(need)))
-    buf = C.create_string_buffer(need.value + 1)
-    check(lib().mpd_last_kernels(buf, need.value + 1, None))
-    return [n for n in buf.value.decode().split("\n") if n]
+    return _postlib.last_kernels(lib().mpd_last_kernels, check)
 
 
 class AtrousDenoiser:
@@ -95,12 +81,7 @@ class AtrousDenoiser:
 
     def __init__(self, resolution, device=0, iterations: int = 5, sigma_normal_pow2: int = 7, sigma_depth: float = 0.2,
                  sigma_luminance: float = 1.5, demodulate_albedo: bool = False, scratch=None):
-        import torch
-
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("the denoiser runs on the GPU")
-        self.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device, self.device_id = _postlib.resolve_device(device, "the denoiser runs on the GPU")
         self.width, self.height = int(resolution[0]), int(resolution[1])
         self.settings = DenoiseSettings(C.sizeof(DenoiseSettings), self.width, self.height, int(iterations), float(sigma_normal_pow2),
                                         float(sigma_depth), float(sigma_luminance), MPD_FLAG_DEMODULATE_ALBEDO if demodulate_albedo else 0)
@@ -113,19 +94,12 @@ class AtrousDenoiser:
         return int(lib().mpd_scratch_floats(C.byref(self.settings), 1 if with_variance else 0))
 
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _postlib.stream_of(self.device)
 
     def _plane(self, t, name):
-        import torch
-
         if t is None:
             return None
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.device.index == self.device_id
-                and tuple(t.shape) == (self.height, self.width, 4) and t.is_contiguous()):
-            raise ValueError(f"{name}: a contiguous float32 [{self.height}, {self.width}, 4] tensor on {self.device} is expected")
-        return t
+        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4))
 
     def denoise(self, color, normal_depth, albedo=None, variance=None, out=None, variance_out=None):
         """mpd_atrous on the current torch stream: `out`, or (`out`, `variance_out`) when a variance plane is given.  The planes

@@ -5,12 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "../../include/minipath_denoise.h"
+#include "../post/post_abi.h"
 
 namespace mpd {
 
@@ -174,67 +171,7 @@ __global__ __launch_bounds__(256) void moments_kernel(const float4* __restrict__
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-static thread_local std::string g_last_kernels;
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(MP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// No exception crosses the C ABI: every extern "C" body runs inside guarded().
-template <class F>
-int guarded(F&& body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        try { g_last_error = "out of host memory (std::bad_alloc)"; } catch (...) {}
-        return MP_ERR_NOMEM;
-    } catch (const std::exception& ex) {
-        try { g_last_error = std::string("unexpected exception: ") + ex.what(); } catch (...) {}
-        return MP_ERR_INVALID;
-    } catch (...) {
-        try { g_last_error = "unexpected exception"; } catch (...) {}
-        return MP_ERR_INVALID;
-    }
-}
-
-// The record of mpd_last_kernels: a call notes each kernel before it launches it, distinct names in launch order.
-struct LaunchLog {
-    std::vector<const char*> names;
-    void note(const char* n) {
-        for (const char* m : names)
-            if (m == n) return;
-        names.push_back(n);
-    }
-    ~LaunchLog() {
-        if (names.empty()) return;
-        try {
-            std::string t;
-            for (const char* n : names) {
-                if (!t.empty()) t += '\n';
-                t += n;
-            }
-            g_last_kernels.swap(t);
-        } catch (...) {}
-    }
-};
-
-// The calling thread's device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 constexpr size_t kSettingsPublished = offsetof(mpd_settings, flags) + sizeof(uint32_t);
 
@@ -272,16 +209,7 @@ size_t mpd_scratch_floats(const mpd_settings* st, int with_variance) {
 }
 
 int mpd_last_kernels(char* buf, size_t cap, size_t* needed) {
-    return guarded([&]() -> int {
-        if (cap && !buf) return fail(MP_ERR_INVALID, "NULL argument");
-        if (needed) *needed = g_last_kernels.size();
-        if (cap) {
-            const size_t n = std::min(cap - 1, g_last_kernels.size());
-            std::memcpy(buf, g_last_kernels.data(), n);
-            buf[n] = 0;
-        }
-        return MP_OK;
-    });
+    return guarded([&]() -> int { return copy_last_kernels(buf, cap, needed); });
 }
 
 int mpd_atrous(int device_id, const mpd_settings* st, const float* d_color, const float* d_normal_depth, const float* d_albedo,
@@ -333,14 +261,9 @@ int mpd_atrous(int device_id, const mpd_settings* st, const float* d_color, cons
             const uint64_t blocks = static_cast<uint64_t>(a.classes_x) * a.tiles_x * a.classes_y * a.tiles_y;
             if (blocks > 0x7FFFFFFFull) return fail(MP_ERR_UNSUPPORTED, "image too large for one launch per pass");
             const dim3 grid(static_cast<uint32_t>(blocks)), block(TILE * TILE);
-            if (variance) {
-                log.note("atrous_kernel<true>");
-                hipLaunchKernelGGL(atrous_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-            } else {
-                log.note("atrous_kernel<false>");
-                hipLaunchKernelGGL(atrous_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-            }
-            if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "atrous_kernel launch");
+            const int rc = variance ? launch(log, "atrous_kernel<true>", atrous_kernel<true>, grid, block, stream, a)
+                                    : launch(log, "atrous_kernel<false>", atrous_kernel<false>, grid, block, stream, a);
+            if (rc != MP_OK) return rc;
         }
         return MP_OK;
     });
@@ -361,12 +284,9 @@ int mpd_variance_from_moments(int device_id, uint32_t width, uint32_t height, ui
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
         LaunchLog log;
-        log.note("moments_kernel");
-        hipLaunchKernelGGL(moments_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           reinterpret_cast<const float4*>(d_shade), reinterpret_cast<const float4*>(d_shade_sq),
-                           reinterpret_cast<float4*>(d_variance), pixels, static_cast<float>(sample_count));
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "moments_kernel launch");
-        return MP_OK;
+        return launch(log, "moments_kernel", moments_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(256), stream,
+                      reinterpret_cast<const float4*>(d_shade), reinterpret_cast<const float4*>(d_shade_sq),
+                      reinterpret_cast<float4*>(d_variance), pixels, static_cast<float>(sample_count));
     });
 }
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from . import _postlib
 from ._lib import MP_OK, MinipathError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -53,18 +54,7 @@ def lib() -> C.CDLL:
     """Load libminipath_resample.so.  Fails loudly when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(RESAMPLE_SO_PATH):
-            raise ImportError(f"{RESAMPLE_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- the resampling has no CPU fallback")
-        try:
-            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
-        except ImportError:
-            pass
-        L = C.CDLL(RESAMPLE_SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _postlib.load(RESAMPLE_SO_PATH, SIGNATURES, "the resampling has no CPU fallback")
     return _lib
 
 
@@ -76,11 +66,7 @@ def check(rc: int) -> None:
 
 def last_kernels() -> list:
     """mpr_last_kernels: the kernel of the calling thread's last launching call."""
-    need = C.c_size_t()
-    check(lib().mpr_last_kernels(None, 0, C.byref(need)))
-    buf = C.create_string_buffer(need.value + 1)
-    check(lib().mpr_last_kernels(buf, need.value + 1, None))
-    return [n for n in buf.value.decode().split("\n") if n]
+    return _postlib.last_kernels(lib().mpr_last_kernels, check)
 
 
 def pointer_array(pointers):
@@ -123,10 +109,7 @@ class GuidedResampler:
 
         if device is None:
             device = torch.cuda.current_device()
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("the resampling runs on the GPU")
-        self.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device, self.device_id = _postlib.resolve_device(device, "the resampling runs on the GPU")
         self.width, self.height = int(resolution[0]), int(resolution[1])
         self.factor = int(factor)
         self.sigma_normal_pow2, self.sigma_plane = float(sigma_normal_pow2), float(sigma_plane)
@@ -142,20 +125,15 @@ class GuidedResampler:
                                 self.sigma_normal_pow2, self.sigma_plane)
 
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _postlib.stream_of(self.device)
 
     def _plane(self, t, name, low=False, words=False):
         import torch
 
         w, h = self.low_resolution if low else (self.width, self.height)
-        dtypes = (torch.float32, torch.int32, torch.uint32) if words else (torch.float32,)
-        if not (isinstance(t, torch.Tensor) and t.dtype in dtypes and t.is_cuda and t.device.index == self.device_id
-                and tuple(t.shape) == (h, w, 4) and t.is_contiguous()):
-            kinds = "float32 or int32" if words else "float32"
-            raise ValueError(f"{name}: a contiguous {kinds} [{h}, {w}, 4] tensor on {self.device} is expected")
-        return t
+        # words: uint32 is taken too, the message names the two kinds callers have
+        dtypes, kinds = ((torch.float32, torch.int32, torch.uint32), "float32 or int32") if words else (None, None)
+        return _postlib.expect_plane(t, name, self.device, self.device_id, (h, w, 4), dtypes, kinds)
 
     def downsample(self, position, normal, *extra, phase: int = 0, pick: str = "phase"):
         """(position_lo, normal_lo, *extra_lo): the planes at each block's picked pixel, bit for bit, zeros where a block has no

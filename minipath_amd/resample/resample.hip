@@ -6,11 +6,9 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "../../include/minipath_resample.h"
+#include "../post/post_abi.h"
 
 namespace mpr {
 
@@ -210,54 +208,7 @@ __global__ __launch_bounds__(TILE * TILE) void upsample_kernel(const UpArgs a) {
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-static thread_local std::string g_last_kernels;
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(MP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// No exception crosses the C ABI: every extern "C" body runs inside guarded().
-template <class F>
-int guarded(F&& body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        try { g_last_error = "out of host memory (std::bad_alloc)"; } catch (...) {}
-        return MP_ERR_NOMEM;
-    } catch (const std::exception& ex) {
-        try { g_last_error = std::string("unexpected exception: ") + ex.what(); } catch (...) {}
-        return MP_ERR_INVALID;
-    } catch (...) {
-        try { g_last_error = "unexpected exception"; } catch (...) {}
-        return MP_ERR_INVALID;
-    }
-}
-
-// The record of mpr_last_kernels: a call notes its kernel before it launches it.  HIP's last-error state is per thread and sticky:
-// an error that earlier work of the process left there is not this launch's, so it is cleared here and what hipGetLastError() says
-// after the launch is the launch's own.
-void note_kernel(const char* name) {
-    g_last_kernels = name;
-    (void)hipGetLastError();
-}
-
-// The calling thread's device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 constexpr size_t kSettingsPublished = offsetof(mpr_settings, sigma_plane) + sizeof(float);
 
@@ -291,22 +242,6 @@ Sizes sizes_of(const mpr_settings* st) {
     return s;
 }
 
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-// Does one of the first n_outs buffers share a byte with another buffer of the list?
-bool outputs_overlap(const Span* s, size_t n, size_t n_outs) {
-    for (size_t o = 0; o < n_outs; ++o) {
-        const uintptr_t ob = reinterpret_cast<uintptr_t>(s[o].p);
-        for (size_t i = o + 1; i < n; ++i) {
-            const uintptr_t ib = reinterpret_cast<uintptr_t>(s[i].p);
-            if (ob < ib ? ib - ob < s[o].bytes : ob - ib < s[i].bytes) return true;
-        }
-    }
-    return false;
-}
-
 }  // namespace
 }  // namespace mpr
 
@@ -336,16 +271,7 @@ int mpr_low_size(const mpr_settings* st, uint32_t* low_width, uint32_t* low_heig
 }
 
 int mpr_last_kernels(char* buf, size_t cap, size_t* needed) {
-    return guarded([&]() -> int {
-        if (cap && !buf) return fail(MP_ERR_INVALID, "NULL argument");
-        if (needed) *needed = g_last_kernels.size();
-        if (cap) {
-            const size_t n = std::min(cap - 1, g_last_kernels.size());
-            std::memcpy(buf, g_last_kernels.data(), n);
-            buf[n] = 0;
-        }
-        return MP_OK;
-    });
+    return guarded([&]() -> int { return copy_last_kernels(buf, cap, needed); });
 }
 
 int mpr_downsample(int device_id, const mpr_settings* st, const float* d_position, const float* d_normal, uint32_t n_planes,
@@ -385,15 +311,9 @@ int mpr_downsample(int device_id, const mpr_settings* st, const float* d_positio
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
         const dim3 grid(static_cast<uint32_t>(blocks)), block(BLOCK);
-        if (st->pick_mode == MPR_PICK_NEAREST) {
-            note_kernel("downsample_kernel<1>");
-            hipLaunchKernelGGL(downsample_kernel<1>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        } else {
-            note_kernel("downsample_kernel<0>");
-            hipLaunchKernelGGL(downsample_kernel<0>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        }
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "downsample_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return st->pick_mode == MPR_PICK_NEAREST ? launch(log, "downsample_kernel<1>", downsample_kernel<1>, grid, block, stream, a)
+                                                 : launch(log, "downsample_kernel<0>", downsample_kernel<0>, grid, block, stream, a);
     });
 }
 
@@ -426,10 +346,8 @@ int mpr_upsample(int device_id, const mpr_settings* st, const float* d_position,
 
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        note_kernel("upsample_kernel");
-        hipLaunchKernelGGL(upsample_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(TILE * TILE), 0, static_cast<hipStream_t>(stream), a);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "upsample_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return launch(log, "upsample_kernel", upsample_kernel, dim3(static_cast<uint32_t>(blocks)), dim3(TILE * TILE), stream, a);
     });
 }
 

@@ -13,6 +13,7 @@ import math
 import os
 
 from . import _lib as _hip
+from . import _postlib
 from ._lib import MP_OK, MinipathError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -50,18 +51,7 @@ def lib() -> C.CDLL:
     """Load libminipath_secondary.so.  Fails loudly when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(SECONDARY_SO_PATH):
-            raise ImportError(f"{SECONDARY_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- the secondary rays have no CPU fallback")
-        try:
-            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
-        except ImportError:
-            pass
-        L = C.CDLL(SECONDARY_SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _postlib.load(SECONDARY_SO_PATH, SIGNATURES, "the secondary rays have no CPU fallback")
     return _lib
 
 
@@ -73,11 +63,7 @@ def check(rc: int) -> None:
 
 def last_kernels() -> list:
     """mps_last_kernels: the kernel of the calling thread's last launching call."""
-    need = C.c_size_t()
-    check(lib().mps_last_kernels(None, 0, C.byref(need)))
-    buf = C.create_string_buffer(need.value + 1)
-    check(lib().mps_last_kernels(buf, need.value + 1, None))
-    return [n for n in buf.value.decode().split("\n") if n]
+    return _postlib.last_kernels(lib().mps_last_kernels, check)
 
 
 class SecondaryVisibility:
@@ -104,17 +90,12 @@ class SecondaryVisibility:
     """
 
     def __init__(self, scene, resolution, device=None, batch: int = 4):
-        import torch
-
         obj = getattr(scene, "object", scene)
         if obj.ctx is None:
             raise MinipathError(1, "host-only BVH cannot be traced: pass a Context to with_obj/build")
         if device is None:
             device = obj.ctx.device_id
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("the secondary rays run on the GPU")
-        self.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device, self.device_id = _postlib.resolve_device(device, "the secondary rays run on the GPU")
         if self.device_id != obj.ctx.device_id:
             raise ValueError(f"the scene lives on device {obj.ctx.device_id}, not {self.device_id}")
         self.scene, self.object = scene, obj
@@ -137,17 +118,10 @@ class SecondaryVisibility:
         return st
 
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _postlib.stream_of(self.device)
 
     def _plane(self, t, name):
-        import torch
-
-        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.device.index == self.device_id
-                and tuple(t.shape) == (self.height, self.width, 4) and t.is_contiguous()):
-            raise ValueError(f"{name}: a contiguous float32 [{self.height}, {self.width}, 4] tensor on {self.device} is expected")
-        return t
+        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4))
 
     def _make_buffers(self):
         import torch

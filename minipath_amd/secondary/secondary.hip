@@ -5,11 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
 
 #include "../../include/minipath_secondary.h"
+#include "../post/post_abi.h"
 #include "../csrc/ray_math.h"
 
 namespace mps {
@@ -136,54 +134,7 @@ __global__ __launch_bounds__(BLOCK) void resolve_kernel(const float* __restrict_
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-static thread_local std::string g_last_kernels;
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(MP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// No exception crosses the C ABI: every extern "C" body runs inside guarded().
-template <class F>
-int guarded(F&& body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        try { g_last_error = "out of host memory (std::bad_alloc)"; } catch (...) {}
-        return MP_ERR_NOMEM;
-    } catch (const std::exception& ex) {
-        try { g_last_error = std::string("unexpected exception: ") + ex.what(); } catch (...) {}
-        return MP_ERR_INVALID;
-    } catch (...) {
-        try { g_last_error = "unexpected exception"; } catch (...) {}
-        return MP_ERR_INVALID;
-    }
-}
-
-// The record of mps_last_kernels: a call notes its kernel before it launches it.  HIP's last-error state is per thread and sticky:
-// an error that earlier work of the process left there is not this launch's, so it is cleared here and what hipGetLastError() says
-// after the launch is the launch's own.
-void note_kernel(const char* name) {
-    g_last_kernels = name;
-    (void)hipGetLastError();
-}
-
-// The calling thread's device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 constexpr size_t kSettingsPublished = offsetof(mps_settings, spread) + sizeof(float);
 
@@ -211,24 +162,6 @@ const char* settings_refusal(const mps_settings* st) {
     return nullptr;
 }
 
-struct Span {
-    const void* p;
-    size_t bytes;
-};
-// Does one of the first n_outs buffers share a byte with another buffer of the list?  NULL buffers are absent.
-bool outputs_overlap(const Span* s, size_t n, size_t n_outs) {
-    for (size_t o = 0; o < n_outs; ++o) {
-        if (!s[o].p) continue;
-        const uintptr_t ob = reinterpret_cast<uintptr_t>(s[o].p);
-        for (size_t i = o + 1; i < n; ++i) {
-            if (!s[i].p) continue;
-            const uintptr_t ib = reinterpret_cast<uintptr_t>(s[i].p);
-            if (ob < ib ? ib - ob < s[o].bytes : ob - ib < s[i].bytes) return true;
-        }
-    }
-    return false;
-}
-
 }  // namespace
 }  // namespace mps
 
@@ -247,16 +180,7 @@ int mps_check_settings(const mps_settings* st) {
 }
 
 int mps_last_kernels(char* buf, size_t cap, size_t* needed) {
-    return guarded([&]() -> int {
-        if (cap && !buf) return fail(MP_ERR_INVALID, "NULL argument");
-        if (needed) *needed = g_last_kernels.size();
-        if (cap) {
-            const size_t n = std::min(cap - 1, g_last_kernels.size());
-            std::memcpy(buf, g_last_kernels.data(), n);
-            buf[n] = 0;
-        }
-        return MP_OK;
-    });
+    return guarded([&]() -> int { return copy_last_kernels(buf, cap, needed); });
 }
 
 int mps_generate(int device_id, const mps_settings* st, const float* d_position, const float* d_normal, float* d_ox, float* d_oy,
@@ -293,15 +217,9 @@ int mps_generate(int device_id, const mps_settings* st, const float* d_position,
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
         const dim3 grid((pixels + BLOCK - 1) / BLOCK), block(BLOCK);
-        if (st->mode == MPS_MODE_SUN) {
-            note_kernel("secondary_rays_kernel<1>");
-            hipLaunchKernelGGL(secondary_rays_kernel<1>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        } else {
-            note_kernel("secondary_rays_kernel<0>");
-            hipLaunchKernelGGL(secondary_rays_kernel<0>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        }
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "secondary_rays_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return st->mode == MPS_MODE_SUN ? launch(log, "secondary_rays_kernel<1>", secondary_rays_kernel<1>, grid, block, stream, a)
+                                        : launch(log, "secondary_rays_kernel<0>", secondary_rays_kernel<0>, grid, block, stream, a);
     });
 }
 
@@ -322,17 +240,11 @@ int mps_resolve(int device_id, const mps_settings* st, const float* d_tmax, cons
         const uint32_t accumulate = (st->flags & MPS_FLAG_ACCUMULATE) ? 1u : 0u;
         float4* counts = reinterpret_cast<float4*>(d_counts);
         float4* out = reinterpret_cast<float4*>(d_out);
-        if (d_out) {
-            note_kernel("resolve_kernel<true>");
-            hipLaunchKernelGGL(resolve_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), d_tmax, d_occluded, counts, out,
-                               pixels, st->batch, accumulate);
-        } else {
-            note_kernel("resolve_kernel<false>");
-            hipLaunchKernelGGL(resolve_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), d_tmax, d_occluded, counts, out,
-                               pixels, st->batch, accumulate);
-        }
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "resolve_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return d_out ? launch(log, "resolve_kernel<true>", resolve_kernel<true>, grid, block, stream, d_tmax, d_occluded, counts, out,
+                              pixels, st->batch, accumulate)
+                     : launch(log, "resolve_kernel<false>", resolve_kernel<false>, grid, block, stream, d_tmax, d_occluded, counts, out,
+                              pixels, st->batch, accumulate);
     });
 }
 

@@ -11,6 +11,7 @@ import os
 
 import numpy as np
 
+from . import _postlib
 from ._lib import MP_OK, MinipathError
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,18 +53,7 @@ def lib() -> C.CDLL:
     """Load libminipath_temporal.so.  Fails loudly when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(TEMPORAL_SO_PATH):
-            raise ImportError(f"{TEMPORAL_SO_PATH} is missing: build it with `make -C minipath_amd/csrc` -- the reprojection has no CPU fallback")
-        try:
-            import torch  # noqa: F401  (one HIP runtime per process: torch's loads first, as for libminipath_hip.so)
-        except ImportError:
-            pass
-        L = C.CDLL(TEMPORAL_SO_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
+        _lib = _postlib.load(TEMPORAL_SO_PATH, SIGNATURES, "the reprojection has no CPU fallback")
     return _lib
 
 
@@ -75,11 +65,7 @@ def check(rc: int) -> None:
 
 def last_kernels() -> list:
     """mpt_last_kernels: the kernel of the calling thread's last launching call."""
-    need = C.c_size_t()
-    check(lib().mpt_last_kernels(None, 0, C.byref(need)))
-    buf = C.create_string_buffer(need.value + 1)
-    check(lib().mpt_last_kernels(buf, need.value + 1, None))
-    return [n for n in buf.value.decode().split("\n") if n]
+    return _postlib.last_kernels(lib().mpt_last_kernels, check)
 
 
 class TemporalAccumulator:
@@ -112,12 +98,7 @@ class TemporalAccumulator:
 
     def __init__(self, resolution, device=0, sigma_position: float = 0.01, normal_min: float = 0.9, max_history: float = 32.0,
                  alpha_color: float = 0.2, alpha_moments: float = 0.2, min_variance_history: float = 4.0, match_prim: bool = False):
-        import torch
-
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError("the reprojection runs on the GPU")
-        self.device_id = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        self.device, self.device_id = _postlib.resolve_device(device, "the reprojection runs on the GPU")
         self.width, self.height = int(resolution[0]), int(resolution[1])
         self.settings = TemporalSettings(C.sizeof(TemporalSettings), self.width, self.height, MPT_FLAG_MATCH_PRIM if match_prim else 0,
                                          float(sigma_position), float(normal_min), float(max_history), float(alpha_color),
@@ -141,21 +122,12 @@ class TemporalAccumulator:
         return v
 
     def _stream(self):
-        import torch
-
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _postlib.stream_of(self.device)
 
     def _plane(self, t, name, dtypes=None):
-        import torch
-
         if t is None:
             return None
-        dtypes = dtypes or (torch.float32,)
-        if not (isinstance(t, torch.Tensor) and t.dtype in dtypes and t.is_cuda and t.device.index == self.device_id
-                and tuple(t.shape) == (self.height, self.width, 4) and t.is_contiguous()):
-            kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
-            raise ValueError(f"{name}: a contiguous {kinds} [{self.height}, {self.width}, 4] tensor on {self.device} is expected")
-        return t
+        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4), dtypes)
 
     def _new_set(self):
         import torch

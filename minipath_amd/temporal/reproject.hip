@@ -5,12 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
 
 #include "../../include/minipath_temporal.h"
+#include "../post/post_abi.h"
 
 namespace mpt {
 
@@ -196,54 +193,7 @@ __global__ __launch_bounds__(TILE_W * TILE_H) void reset_kernel(const float4* __
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-static thread_local std::string g_last_error;
-static thread_local std::string g_last_kernels;
-
 namespace {
-
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-int hip_fail(hipError_t e, const char* what) { return fail(MP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-
-// No exception crosses the C ABI: every extern "C" body runs inside guarded().
-template <class F>
-int guarded(F&& body) noexcept {
-    try {
-        return body();
-    } catch (const std::bad_alloc&) {
-        try { g_last_error = "out of host memory (std::bad_alloc)"; } catch (...) {}
-        return MP_ERR_NOMEM;
-    } catch (const std::exception& ex) {
-        try { g_last_error = std::string("unexpected exception: ") + ex.what(); } catch (...) {}
-        return MP_ERR_INVALID;
-    } catch (...) {
-        try { g_last_error = "unexpected exception"; } catch (...) {}
-        return MP_ERR_INVALID;
-    }
-}
-
-// The record of mpt_last_kernels: a call notes its kernel before it launches it.  HIP's last-error state is per thread and sticky:
-// an error that earlier work of the process left there (any library, any call whose status nobody read) is not this launch's, so
-// it is cleared here and what hipGetLastError() says after the launch is the launch's own.
-void note_kernel(const char* name) {
-    g_last_kernels = name;
-    (void)hipGetLastError();
-}
-
-// The calling thread's device is put back when the call returns.
-struct DeviceScope {
-    int prev = -1;
-    hipError_t enter(int device) {
-        hipError_t e = hipGetDevice(&prev);
-        if (e != hipSuccess) { prev = -1; return e; }
-        return hipSetDevice(device);
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
 
 constexpr size_t kSettingsPublished = offsetof(mpt_settings, min_variance_history) + sizeof(float);
 
@@ -268,19 +218,12 @@ const char* settings_refusal(const mpt_settings* st) {
     return nullptr;
 }
 
-// Does an output plane share a byte with another plane of the call?  outs come first in `planes`; NULL planes are absent.
-bool outputs_overlap(const void* const* planes, size_t n_planes, size_t n_outs, size_t bytes) {
-    for (size_t o = 0; o < n_outs; ++o) {
-        if (!planes[o]) continue;
-        const uintptr_t ob = reinterpret_cast<uintptr_t>(planes[o]);
-        for (size_t i = o + 1; i < n_planes; ++i) {
-            if (!planes[i]) continue;
-            const uintptr_t ib = reinterpret_cast<uintptr_t>(planes[i]);
-            const uintptr_t lo = ob < ib ? ob : ib, hi = ob < ib ? ib : ob;
-            if (hi - lo < bytes) return true;
-        }
-    }
-    return false;
+// Does one of the first n_outs planes, all of `bytes` bytes, share a byte with another plane of the call?  NULL planes are absent.
+template <size_t N>
+bool planes_overlap(const void* const (&planes)[N], size_t n_outs, size_t bytes) {
+    Span spans[N];
+    for (size_t i = 0; i < N; ++i) spans[i] = {planes[i], bytes};
+    return outputs_overlap(spans, N, n_outs);
 }
 
 // the grid of one block per tile; 0 when it is more than one launch can hold
@@ -308,16 +251,7 @@ int mpt_check_settings(const mpt_settings* st) {
 }
 
 int mpt_last_kernels(char* buf, size_t cap, size_t* needed) {
-    return guarded([&]() -> int {
-        if (cap && !buf) return fail(MP_ERR_INVALID, "NULL argument");
-        if (needed) *needed = g_last_kernels.size();
-        if (cap) {
-            const size_t n = std::min(cap - 1, g_last_kernels.size());
-            std::memcpy(buf, g_last_kernels.data(), n);
-            buf[n] = 0;
-        }
-        return MP_OK;
-    });
+    return guarded([&]() -> int { return copy_last_kernels(buf, cap, needed); });
 }
 
 int mpt_reproject(int device_id, const mpt_settings* st, const mpt_view* prev_view, const float* d_color, const float* d_position,
@@ -335,7 +269,7 @@ int mpt_reproject(int device_id, const mpt_settings* st, const mpt_view* prev_vi
         const uint32_t W = st->width, H = st->height;
         const void* planes[] = {d_out, d_moments_out, d_variance_out, d_color, d_position, d_normal, d_ids, d_variance_in,
                                 d_prev_position, d_prev_normal, d_prev_ids, d_hist_color, d_hist_moments};
-        if (outputs_overlap(planes, sizeof(planes) / sizeof(planes[0]), 3, static_cast<size_t>(W) * H * 16))
+        if (planes_overlap(planes, 3, static_cast<size_t>(W) * H * 16))
             return fail(MP_ERR_INVALID, "an output overlaps another plane of the call");
         Args a{};
         const uint32_t blocks = grid_of(W, H, a.tiles_x);
@@ -367,15 +301,9 @@ int mpt_reproject(int device_id, const mpt_settings* st, const mpt_view* prev_vi
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
         const dim3 grid(blocks), block(TILE_W * TILE_H);
-        if (d_variance_in) {
-            note_kernel("reproject_kernel<true>");
-            hipLaunchKernelGGL(reproject_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        } else {
-            note_kernel("reproject_kernel<false>");
-            hipLaunchKernelGGL(reproject_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), a);
-        }
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "reproject_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return d_variance_in ? launch(log, "reproject_kernel<true>", reproject_kernel<true>, grid, block, stream, a)
+                             : launch(log, "reproject_kernel<false>", reproject_kernel<false>, grid, block, stream, a);
     });
 }
 
@@ -386,19 +314,17 @@ int mpt_reset(int device_id, uint32_t width, uint32_t height, const float* d_col
         if (const char* why = dims_refusal(width, height)) return fail(MP_ERR_INVALID, why);
         if (device_id < 0) return fail(MP_ERR_INVALID, "negative device_id");
         const void* planes[] = {d_out, d_moments_out, d_color, d_position};
-        if (outputs_overlap(planes, 4, 2, static_cast<size_t>(width) * height * 16))
+        if (planes_overlap(planes, 2, static_cast<size_t>(width) * height * 16))
             return fail(MP_ERR_INVALID, "an output overlaps another plane of the call");
         uint32_t tiles_x;
         const uint32_t blocks = grid_of(width, height, tiles_x);
         if (!blocks) return fail(MP_ERR_UNSUPPORTED, "image too large for one launch");
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");
-        note_kernel("reset_kernel");
-        hipLaunchKernelGGL(reset_kernel, dim3(blocks), dim3(TILE_W * TILE_H), 0, static_cast<hipStream_t>(stream),
-                           reinterpret_cast<const float4*>(d_color), reinterpret_cast<const float4*>(d_position),
-                           reinterpret_cast<float4*>(d_out), reinterpret_cast<float4*>(d_moments_out), width, height, tiles_x);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return hip_fail(e, "reset_kernel launch");
-        return MP_OK;
+        LaunchLog log;
+        return launch(log, "reset_kernel", reset_kernel, dim3(blocks), dim3(TILE_W * TILE_H), stream,
+                      reinterpret_cast<const float4*>(d_color), reinterpret_cast<const float4*>(d_position),
+                      reinterpret_cast<float4*>(d_out), reinterpret_cast<float4*>(d_moments_out), width, height, tiles_x);
     });
 }
 
