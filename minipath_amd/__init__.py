@@ -15,9 +15,10 @@ from .adaptive import AdaptiveSampler  # noqa: F401  (adaptive/libminipath_adapt
 from .temporal import TemporalAccumulator  # noqa: F401  (temporal/libminipath_temporal.so is loaded on first use, not here)
 from .secondary import SecondaryVisibility  # noqa: F401  (secondary/libminipath_secondary.so is loaded on first use, not here)
 from .resample import GuidedResampler  # noqa: F401  (resample/libminipath_resample.so is loaded on first use, not here)
+from .lights import LocalLights  # noqa: F401  (lights/libminipath_lights.so is loaded on first use, not here)
 
 __all__ = [
-    "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "GuidedResampler", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
+    "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "GuidedResampler", "LocalLights", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
     "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "SecondaryVisibility", "Sphere", "TemporalAccumulator", "TriangleBvh", "render", "render_tile",
     "tile_ordering",
 ]

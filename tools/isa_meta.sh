@@ -1,12 +1,13 @@
 #!/bin/bash
 # Per-kernel register / spill / scratch metadata of gfx950 code objects (device-only compiles with the Makefile's flags, then the
-# AMDGPU metadata notes).  usage: tools/isa_meta.sh [denoise|adaptive|temporal|secondary|resample] > profiles/rNN_isa_meta.txt
+# AMDGPU metadata notes).  usage: tools/isa_meta.sh [denoise|adaptive|temporal|secondary|resample|lights] > profiles/rNN_isa_meta.txt
 #   (no argument)  the code objects of libminipath_hip.so, one per translation unit (kernels*.hip), as one list sorted by kernel
 #   denoise        ../denoise/atrous.hip, the code object of libminipath_denoise.so -> profiles/denoise/isa_meta.txt
 #   adaptive       ../adaptive/adaptive.hip, the code object of libminipath_adaptive.so -> profiles/adaptive/isa_meta.txt
 #   temporal       ../temporal/reproject.hip, the code object of libminipath_temporal.so -> profiles/temporal/isa_meta.txt
 #   secondary      ../secondary/secondary.hip, the code object of libminipath_secondary.so -> profiles/secondary/isa_meta.txt
 #   resample       ../resample/resample.hip, the code object of libminipath_resample.so -> profiles/resample/isa_meta.txt
+#   lights         ../lights/lights.hip, the code object of libminipath_lights.so -> profiles/lights/isa_meta.txt
 set -e
 cd "$(dirname "$0")/../minipath_amd/csrc"
 if [ "$1" = denoise ]; then
@@ -24,6 +25,9 @@ elif [ "$1" = secondary ]; then
 elif [ "$1" = resample ]; then
   make -s ../resample/resample.gfx950.co
   COS=../resample/resample.gfx950.co
+elif [ "$1" = lights ]; then
+  make -s ../lights/lights.gfx950.co
+  COS=../lights/lights.gfx950.co
 else
   make -s code-objects
   COS=$(echo kernels*.gfx950.co)
