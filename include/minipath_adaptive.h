@@ -16,7 +16,8 @@
  *   - every refusal is decided before the first HIP call: a refused call launches nothing and writes nothing.
  *
  * Planes are TILE-MAJOR, as the render writes them: with ts = tile_size, slot i starts at float index i * ts * ts * 4, and pixel
- * (x, y) of a slot sits at (y * ts + x) * 4 from there (16 bytes per pixel).  The extent (w, h) of slot i is d_tile_wh[i] = {w, h}
+ * (x, y) of a slot sits at (y * ts + x) * 4 from there (16 bytes per pixel).  A plane buffer (d_shade, d_shade_sq, d_src, d_dst, d_plane) is
+ * 16-byte aligned: one that is not is refused (MP_ERR_INVALID) before the first HIP call.  The extent (w, h) of slot i is d_tile_wh[i] = {w, h}
  * (u32[n][2]; a value above ts counts as ts): the slot OWNS the pixels x < w, y < h.  The rest of the slot is neither read nor
  * written by mpa_tile_error and mpa_finish_tiles; mpa_move_tiles moves whole slots. */
 #ifndef MINIPATH_ADAPTIVE_H

@@ -114,7 +114,8 @@ size_t mpd_scratch_floats(const mpd_settings *settings, int with_variance);
 /* The filter above.  The inputs are only read; d_out (and d_variance_out) must not overlap anything else passed.
  *   d_albedo       nullable unless MPD_FLAG_DEMODULATE_ALBEDO
  *   d_variance     nullable: without it the luminance weight uses sigma_luminance alone and no variance is propagated
- *   d_scratch      mpd_scratch_floats(settings, d_variance != NULL) floats, 16-byte aligned like every plane
+ *   d_scratch      mpd_scratch_floats(settings, d_variance != NULL) floats, 16-byte aligned like every plane: a misaligned plane
+ *                  is refused (MP_ERR_INVALID) before the first HIP call
  *   d_variance_out nullable; must be NULL when d_variance is
  * MP_ERR_INVALID: a NULL settings / d_color / d_normal_depth / d_scratch / d_out, width * height == 0, a width or height above
  * MPD_MAX_DIM, iterations outside 1..8, sigma_normal_pow2 not a whole number in 0..8, a sigma that is not > 0 (NaN included), a

@@ -11,7 +11,8 @@
  *   - every function that can fail returns an int status, MP_OK == 0, with the values of minipath_hip.h; no exception or abort
  *     crosses the ABI (every body runs inside a catch-all: std::bad_alloc -> MP_ERR_NOMEM, anything else -> MP_ERR_INVALID); the
  *     message of the last failure on the calling thread is mpt_last_error();
- *   - "d_" pointers are device (HBM) pointers on the GPU `device_id`, 16-byte aligned;
+ *   - "d_" pointers are device (HBM) pointers on the GPU `device_id`, 16-byte aligned: a pointer that is
+ *     not is refused (MP_ERR_INVALID) before the first HIP call;
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); every call is asynchronous on it;
  *   - every plane is image-major [height][width][4], 16 bytes per pixel, as mp_untile writes it (FrameRenderer.untile_plane): pixel
  *     (x, y) is at element index (y * width + x) * 4.

@@ -7,6 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+PLANE_ALIGN = 16  # bytes: what the libraries ask of every plane's first byte
 
 def load(path: str, signatures: dict, what: str) -> C.CDLL:
     """The library at `path` with restype and argtypes set from `signatures` (name -> (restype, argtypes)).  `what` ends the
@@ -53,13 +54,18 @@ def stream_of(device) -> C.c_void_p:
 
 
 def expect_plane(t, name: str, device, device_id: int, shape, dtypes=None, kinds=None):
-    """`t` if it is a contiguous tensor of `shape` and one of `dtypes` (default: float32) on the device, else ValueError.
+    """`t` if it is a contiguous tensor of `shape` and one of `dtypes` (default: float32) on the device whose first byte is 16-byte
+    aligned (the libraries read and write a plane as 16-byte pixels and refuse any other), else ValueError.  A fresh tensor and a
+    view that starts a whole number of pixels into one are aligned; a view that starts at an odd float is not.
     `kinds`: how the message names the dtypes, where that is not their names joined by " or "."""
     import torch
 
     dtypes = dtypes or (torch.float32,)
+    kinds = kinds or " or ".join(str(d).replace("torch.", "") for d in dtypes)
     if not (isinstance(t, torch.Tensor) and t.dtype in dtypes and t.is_cuda and t.device.index == device_id
             and tuple(t.shape) == tuple(shape) and t.is_contiguous()):
-        kinds = kinds or " or ".join(str(d).replace("torch.", "") for d in dtypes)
         raise ValueError(f"{name}: a contiguous {kinds} {list(shape)} tensor on {device} is expected")
+    if t.data_ptr() % PLANE_ALIGN:
+        raise ValueError(f"{name}: a contiguous, {PLANE_ALIGN}-byte aligned {kinds} {list(shape)} tensor on {device} is expected "
+                         f"(this one starts {t.data_ptr() % PLANE_ALIGN} bytes past a {PLANE_ALIGN}-byte boundary)")
     return t

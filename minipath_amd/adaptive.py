@@ -84,7 +84,9 @@ class AdaptiveSampler:
     between rounds: they and `samples` are the checkpoint of the render.
 
     One host synchronisation per round is inherent: the tile list of the next pass is a host argument of
-    mp_render_aov_pass_device, so the host reads the round's `open` counts before it can issue the next round.  While every tile is
+    mp_render_aov_pass_device, so the host reads the round's `open` counts before it can issue the next round.  It is the only one:
+    a round without a check (the last) and finish() are enqueued on the current torch stream without waiting for it, once the
+    context holds the round's tile list (a list it has not seen is uploaded with a blocking copy, once).  While every tile is
     active the passes render straight into the canonical planes; afterwards the active slots are gathered into compact work planes
     (mpa_move_tiles), rendered and checked there, and scattered back.
 
@@ -136,6 +138,14 @@ class AdaptiveSampler:
     def _stream(self):
         return _postlib.stream_of(self.device)
 
+    def _upload(self, a):
+        """A small host array on the device through pinned memory, asynchronous on the current torch stream.  (A copy from pageable
+        memory blocks the calling thread until the stream has drained: a host synchronisation at the head of every compact round
+        and in finish().)"""
+        import torch
+
+        return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(self.device, non_blocking=True)
+
     def _move(self, n, src, src_idx, dst, dst_idx):
         check(lib().mpa_move_tiles(self.device_id, int(self.settings.tile_size), n, src.data_ptr(), src.shape[0],
                                    None if src_idx is None else src_idx.data_ptr(), dst.data_ptr(), dst.shape[0],
@@ -173,8 +183,8 @@ class AdaptiveSampler:
             if self._work is None:
                 self._work = {k: torch.zeros_like(self.planes[k]) for k in names}
             target = {k: self._work[k] for k in names}
-            d_idx = torch.from_numpy(act).to(self.device)
-            d_wh = torch.from_numpy(np.ascontiguousarray(self._wh[act])).to(self.device)
+            d_idx = self._upload(act)
+            d_wh = self._upload(self._wh[act])
             tiles_c = (_lib.Block * n)(*[self.fr.tiles[i].as_struct() for i in self.active])
             for k in names:
                 self._move(n, self.planes[k], d_idx, target[k], None)
@@ -205,7 +215,7 @@ class AdaptiveSampler:
 
         if self.finished:
             return
-        d_samples = torch.from_numpy(self.samples.astype(np.int32)).to(self.device)
+        d_samples = self._upload(self.samples.astype(np.int32))
         for k, p in self.planes.items():
             if p.dtype == torch.float32:
                 check(lib().mpa_finish_tiles(self.device_id, int(self.settings.tile_size), self.n_tiles, self.bounds[-1], p.data_ptr(),

@@ -172,6 +172,7 @@ int mpa_tile_error(int device_id, uint32_t tile_size, uint32_t n_slots, uint32_t
         for (const void* in : inputs)
             if (in == d_open || in == d_max_err) return fail(MP_ERR_INVALID, "an output aliases an input");
         if (static_cast<const void*>(d_open) == static_cast<const void*>(d_max_err)) return fail(MP_ERR_INVALID, "d_max_err aliases d_open");
+        if (!all_aligned({d_shade, d_shade_sq}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         if (tile_size > MPA_MAX_TILE_SIZE) return fail(MP_ERR_UNSUPPORTED, "tile_size above MPA_MAX_TILE_SIZE");
         if (n_slots > kMaxBlocks) return fail(MP_ERR_UNSUPPORTED, "too many slots for one launch");
         const float r = 1.0f / static_cast<float>(samples_done);
@@ -192,6 +193,7 @@ int mpa_move_tiles(int device_id, uint32_t tile_size, uint32_t n, const void* d_
         if (d_src == d_dst) return fail(MP_ERR_INVALID, "d_src == d_dst");
         if (tile_size == 0 || src_slots == 0 || dst_slots == 0) return fail(MP_ERR_INVALID, "tile_size, src_slots or dst_slots is 0");
         if (device_id < 0) return fail(MP_ERR_INVALID, "negative device_id");
+        if (!all_aligned({d_src, d_dst}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         if (tile_size > MPA_MAX_TILE_SIZE) return fail(MP_ERR_UNSUPPORTED, "tile_size above MPA_MAX_TILE_SIZE");
         const uint32_t per_tile = tile_size * tile_size;
         const uint64_t chunks = (static_cast<uint64_t>(per_tile) + CHUNK - 1) / CHUNK;
@@ -215,6 +217,7 @@ int mpa_finish_tiles(int device_id, uint32_t tile_size, uint32_t n_slots, uint32
         if (device_id < 0) return fail(MP_ERR_INVALID, "negative device_id");
         if (static_cast<const void*>(d_plane) == d_samples || static_cast<const void*>(d_plane) == d_tile_wh)
             return fail(MP_ERR_INVALID, "d_plane aliases an input");
+        if (!all_aligned({d_plane}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         if (tile_size > MPA_MAX_TILE_SIZE) return fail(MP_ERR_UNSUPPORTED, "tile_size above MPA_MAX_TILE_SIZE");
         const uint32_t per_tile = tile_size * tile_size;
         const uint64_t chunks = (static_cast<uint64_t>(per_tile) + CHUNK - 1) / CHUNK;

@@ -225,6 +225,8 @@ int mpd_atrous(int device_id, const mpd_settings* st, const float* d_color, cons
         for (const void* o : others)
             if (o && (o == d_out || o == d_variance_out)) return fail(MP_ERR_INVALID, "an output aliases another argument");
         if (d_variance_out == d_out) return fail(MP_ERR_INVALID, "d_variance_out aliases d_out");
+        if (!all_aligned({d_color, d_normal_depth, d_albedo, d_variance, d_scratch, d_out, d_variance_out}, kPlaneAlign))
+            return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
 
         const uint32_t W = st->width, H = st->height;
         const size_t plane = static_cast<size_t>(W) * H;  // in pixels (float4)
@@ -278,6 +280,7 @@ int mpd_variance_from_moments(int device_id, uint32_t width, uint32_t height, ui
         if (sample_count == 0) return fail(MP_ERR_INVALID, "sample_count == 0");
         if (device_id < 0) return fail(MP_ERR_INVALID, "negative device_id");
         if (d_variance == d_shade || d_variance == d_shade_sq) return fail(MP_ERR_INVALID, "d_variance aliases an input");
+        if (!all_aligned({d_shade, d_shade_sq, d_variance}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         const size_t pixels = static_cast<size_t>(width) * height;
         const size_t blocks = (pixels + 255) / 256;
         if (blocks > 0x7FFFFFFFull) return fail(MP_ERR_UNSUPPORTED, "image too large for one launch");

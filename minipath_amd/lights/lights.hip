@@ -238,6 +238,9 @@ int mpl_generate(int device_id, const mpl_settings* st, const mpl_light* lights,
         const Span spans[] = {{d_ox, rays}, {d_oy, rays}, {d_oz, rays}, {d_dx, rays}, {d_dy, rays}, {d_dz, rays}, {d_tmax, rays},
                               {d_weight, rays}, {d_position, plane}, {d_normal, plane}};
         if (outputs_overlap(spans, 10, 8)) return fail(MP_ERR_INVALID, "a ray array overlaps another buffer of the call");
+        if (!all_aligned({d_position, d_normal}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax, d_weight}, kWordAlign))
+            return fail(MP_ERR_INVALID, "a ray array is not 4-byte aligned");
         GenArgs a{};
         a.position = reinterpret_cast<const float4*>(d_position);
         a.normal = reinterpret_cast<const float4*>(d_normal);
@@ -277,6 +280,8 @@ int mpl_resolve(int device_id, const mpl_settings* st, const mpl_light* lights, 
         const size_t rays = static_cast<size_t>(pixels) * st->batch * st->light_count, plane = static_cast<size_t>(pixels) * 16;
         const Span spans[] = {{d_sums, plane}, {d_out, plane}, {d_tmax, rays * 4}, {d_weight, rays * 4}, {d_occluded, rays}};
         if (outputs_overlap(spans, 5, 2)) return fail(MP_ERR_INVALID, "an output overlaps another buffer of the call");
+        if (!all_aligned({d_sums, d_out}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_tmax, d_weight}, kWordAlign)) return fail(MP_ERR_INVALID, "a ray array is not 4-byte aligned");
         ResArgs a{};
         a.tmax = d_tmax;
         a.weight = d_weight;

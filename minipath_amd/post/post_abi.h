@@ -1,6 +1,6 @@
 // The host side every post-process library (denoise, adaptive, temporal, secondary, resample) puts between its C ABI and its
 // kernels: the last-error and last-kernels records, the catch-all of an extern "C" body, the device scope, the launch and the
-// overlap check of a call's buffers.  Include it after the library's own header under include/ (the MP_* status values).
+// overlap and alignment checks of a call's buffers.  Include it after the library's own header under include/ (the MP_* status values).
 // Everything here has internal linkage: each shared object that includes this keeps thread-local records of its own, and two
 // libraries loaded into one process share nothing.
 #pragma once
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -118,6 +119,16 @@ bool outputs_overlap(const Span* s, size_t n, size_t n_outs) {
         }
     }
     return false;
+}
+
+// The alignment a header states is refused where it is missing, not left to the device: a plane is read and written as 16-byte
+// pixels (kPlaneAlign), a ray array or a pick array as 32-bit words (kWordAlign).  Is every pointer of the list a multiple of
+// `align` (a power of two)?  NULL pointers are absent.
+constexpr uintptr_t kPlaneAlign = 16, kWordAlign = 4;
+bool all_aligned(std::initializer_list<const void*> ptrs, uintptr_t align) {
+    for (const void* p : ptrs)
+        if (reinterpret_cast<uintptr_t>(p) & (align - 1)) return false;
+    return true;
 }
 
 }  // namespace

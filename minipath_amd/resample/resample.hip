@@ -294,6 +294,10 @@ int mpr_downsample(int device_id, const mpr_settings* st, const float* d_positio
         spans[n++] = {d_normal, plane};
         for (uint32_t i = 0; i < n_planes; ++i) spans[n++] = {d_sources[i], plane};
         if (outputs_overlap(spans, n, n_outs)) return fail(MP_ERR_INVALID, "an output overlaps another buffer of the call");
+        bool planes_aligned = all_aligned({d_position, d_normal}, kPlaneAlign);
+        for (uint32_t i = 0; i < n_planes; ++i) planes_aligned = planes_aligned && all_aligned({d_sources[i], d_destinations[i]}, kPlaneAlign);
+        if (!planes_aligned) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_picks}, kWordAlign)) return fail(MP_ERR_INVALID, "d_picks is not 4-byte aligned");
         DownArgs a{};
         a.position = reinterpret_cast<const float4*>(d_position);
         a.normal = reinterpret_cast<const float4*>(d_normal);
@@ -329,6 +333,9 @@ int mpr_upsample(int device_id, const mpr_settings* st, const float* d_position,
         const Span spans[] = {{d_out, plane}, {d_position, plane}, {d_normal, plane}, {d_position_lo, plane_lo}, {d_normal_lo, plane_lo},
                               {d_color_lo, plane_lo}, {d_picks, static_cast<size_t>(s.low) * 4}};
         if (outputs_overlap(spans, 7, 1)) return fail(MP_ERR_INVALID, "d_out overlaps another buffer of the call");
+        if (!all_aligned({d_out, d_position, d_normal, d_position_lo, d_normal_lo, d_color_lo}, kPlaneAlign))
+            return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_picks}, kWordAlign)) return fail(MP_ERR_INVALID, "d_picks is not 4-byte aligned");
         UpArgs a{};
         a.position = reinterpret_cast<const float4*>(d_position);
         a.normal = reinterpret_cast<const float4*>(d_normal);

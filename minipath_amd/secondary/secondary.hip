@@ -195,6 +195,9 @@ int mps_generate(int device_id, const mps_settings* st, const float* d_position,
         const Span spans[] = {{d_ox, rays}, {d_oy, rays}, {d_oz, rays}, {d_dx, rays}, {d_dy, rays}, {d_dz, rays}, {d_tmax, rays},
                               {d_position, plane}, {d_normal, plane}};
         if (outputs_overlap(spans, 9, 7)) return fail(MP_ERR_INVALID, "a ray array overlaps another buffer of the call");
+        if (!all_aligned({d_position, d_normal}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_ox, d_oy, d_oz, d_dx, d_dy, d_dz, d_tmax}, kWordAlign))
+            return fail(MP_ERR_INVALID, "a ray array is not 4-byte aligned");
         GenArgs a{};
         a.position = reinterpret_cast<const float4*>(d_position);
         a.normal = reinterpret_cast<const float4*>(d_normal);
@@ -233,6 +236,8 @@ int mps_resolve(int device_id, const mps_settings* st, const float* d_tmax, cons
         const size_t rays = static_cast<size_t>(pixels) * st->batch, plane = static_cast<size_t>(pixels) * 16;
         const Span spans[] = {{d_counts, plane}, {d_out, plane}, {d_tmax, rays * 4}, {d_occluded, rays}};
         if (outputs_overlap(spans, 4, 2)) return fail(MP_ERR_INVALID, "an output overlaps another buffer of the call");
+        if (!all_aligned({d_counts, d_out}, kPlaneAlign)) return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
+        if (!all_aligned({d_tmax}, kWordAlign)) return fail(MP_ERR_INVALID, "a ray array is not 4-byte aligned");
 
         DeviceScope dev;
         if (hipError_t e = dev.enter(device_id); e != hipSuccess) return hip_fail(e, "hipSetDevice");

@@ -271,6 +271,9 @@ int mpt_reproject(int device_id, const mpt_settings* st, const mpt_view* prev_vi
                                 d_prev_position, d_prev_normal, d_prev_ids, d_hist_color, d_hist_moments};
         if (planes_overlap(planes, 3, static_cast<size_t>(W) * H * 16))
             return fail(MP_ERR_INVALID, "an output overlaps another plane of the call");
+        if (!all_aligned({d_out, d_moments_out, d_variance_out, d_color, d_position, d_normal, d_ids, d_variance_in, d_prev_position,
+                          d_prev_normal, d_prev_ids, d_hist_color, d_hist_moments}, kPlaneAlign))
+            return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         Args a{};
         const uint32_t blocks = grid_of(W, H, a.tiles_x);
         if (!blocks) return fail(MP_ERR_UNSUPPORTED, "image too large for one launch");
@@ -316,6 +319,8 @@ int mpt_reset(int device_id, uint32_t width, uint32_t height, const float* d_col
         const void* planes[] = {d_out, d_moments_out, d_color, d_position};
         if (planes_overlap(planes, 2, static_cast<size_t>(width) * height * 16))
             return fail(MP_ERR_INVALID, "an output overlaps another plane of the call");
+        if (!all_aligned({d_out, d_moments_out, d_color, d_position}, kPlaneAlign))
+            return fail(MP_ERR_INVALID, "a plane is not 16-byte aligned");
         uint32_t tiles_x;
         const uint32_t blocks = grid_of(width, height, tiles_x);
         if (!blocks) return fail(MP_ERR_UNSUPPORTED, "image too large for one launch");

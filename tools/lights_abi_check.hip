@@ -72,6 +72,23 @@ int resolve(const mpl_settings* st, const mpl_light* lt, Buffers& b, int dev = D
                        out ? out : b.out.get(), nullptr);
 }
 
+// the calls with nothing wrong but buffer `at` (in the order of the arguments) moved by `by` bytes
+char* moved(void* p, int by) { return static_cast<char*>(p) + by; }
+int generate_moved(const mpl_settings* st, const mpl_light* lt, Buffers& b, int at, int by) {
+    void* p[10] = {b.position.get(), b.normal.get(), b.ray[0].get(), b.ray[1].get(), b.ray[2].get(), b.ray[3].get(), b.ray[4].get(),
+                   b.ray[5].get(), b.ray[6].get(), b.ray[7].get()};
+    p[at] = moved(p[at], by);
+    float* f[10];
+    for (int i = 0; i < 10; ++i) f[i] = static_cast<float*>(p[i]);
+    return mpl_generate(DEV, st, lt, f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8], f[9], nullptr);
+}
+int resolve_moved(const mpl_settings* st, const mpl_light* lt, Buffers& b, int at, int by) {
+    void* p[5] = {b.ray[6].get(), b.ray[7].get(), b.occluded.get(), b.sums.get(), b.out.get()};
+    p[at] = moved(p[at], by);
+    return mpl_resolve(DEV, st, lt, static_cast<float*>(p[0]), static_cast<float*>(p[1]), static_cast<uint8_t*>(p[2]), static_cast<float*>(p[3]),
+                       static_cast<float*>(p[4]), nullptr);
+}
+
 }  // namespace
 
 int main() {
@@ -180,6 +197,20 @@ int main() {
     EXPECT(resolve(&good, lights.get(), b, DEV, -1, b.sums.get()) == MP_ERR_INVALID);                   // out == sums
     EXPECT(resolve(&good, lights.get(), b, DEV, -1, b.ray[7].get() + 8) == MP_ERR_INVALID);             // out inside weight
     EXPECT(g_last_error == "an output overlaps another buffer of the call");
+
+    // alignment, after the NULL and overlap checks: a plane 4, 8 or 12 bytes off, a ray array 1, 2 or 3 bytes off (a refused
+    // call reads and writes none of its buffers)
+    for (void* p : {static_cast<void*>(b.position.get()), static_cast<void*>(b.normal.get()), static_cast<void*>(b.sums.get()), static_cast<void*>(b.out.get())})
+        EXPECT(reinterpret_cast<uintptr_t>(p) % 16 == 0);
+    for (int by : {4, 8, 12}) {
+        for (int at : {0, 1}) EXPECT(generate_moved(&good, lights.get(), b, at, by) == MP_ERR_INVALID && g_last_error == "a plane is not 16-byte aligned");
+        for (int at : {3, 4}) EXPECT(resolve_moved(&good, lights.get(), b, at, by) == MP_ERR_INVALID && g_last_error == "a plane is not 16-byte aligned");
+    }
+    for (int by : {1, 2, 3}) {
+        for (int at = 2; at < 10; ++at)
+            EXPECT(generate_moved(&good, lights.get(), b, at, by) == MP_ERR_INVALID && g_last_error == "a ray array is not 4-byte aligned");
+        for (int at : {0, 1}) EXPECT(resolve_moved(&good, lights.get(), b, at, by) == MP_ERR_INVALID && g_last_error == "a ray array is not 4-byte aligned");
+    }
 
     // nothing above launched anything or wrote a word
     size_t need = 99;
