@@ -239,10 +239,9 @@ __device__ __forceinline__ bool may_hit_scene(const DevScene& sc, const Ray& r) 
     return t1 <= t2;
 }
 
-// Hit resolve + shade: tail of intersect (ray_bvh_intersection.rs:66-95) and render_sample (worker.rs:59-65).
-// Returns |dot(ray.direction, normal)|.
-// Returns TriangleShadingData.material of the triangle (mod.rs:44; 0 for everything the reference builds).
-__device__ __forceinline__ uint32_t resolve_normal(const DevScene& sc, uint32_t prim, float u, float v, float n[3]) {
+// The triangle's un-normalised normal at (u, v); returns its material (below).  (Handed back through an array: with three reference
+// parameters resolve_normal's callers compiled to other code -- swapped operands of an add in 64 kernels, tools/kernel_code_diff.py.)
+__device__ __forceinline__ uint32_t raw_normal(const DevScene& sc, uint32_t prim, float u, float v, float raw[3]) {
     const float4* sh = reinterpret_cast<const float4*>(sc.shade) + static_cast<size_t>(prim) * 3;
     float4 a = sh[0], b = sh[1], c = sh[2];
     float nx, ny, nz;
@@ -259,9 +258,29 @@ __device__ __forceinline__ uint32_t resolve_normal(const DevScene& sc, uint32_t 
         ny = a.y * w + b.x * u + b.w * v;
         nz = a.z * w + b.y * u + c.x * v;
     }
+    raw[0] = nx; raw[1] = ny; raw[2] = nz;
+    return as_u(c.z);
+}
+// Hit resolve + shade: tail of intersect (ray_bvh_intersection.rs:66-95) and render_sample (worker.rs:59-65).
+// Returns |dot(ray.direction, normal)|.
+// Returns TriangleShadingData.material of the triangle (mod.rs:44; 0 for everything the reference builds).
+__device__ __forceinline__ uint32_t resolve_normal(const DevScene& sc, uint32_t prim, float u, float v, float n[3]) {
+    float raw[3];
+    const uint32_t mat = raw_normal(sc, prim, u, v, raw);
+    const float nx = raw[0], ny = raw[1], nz = raw[2];
     float len = sqrtf(nx * nx + ny * ny + nz * nz);
     n[0] = nx / len; n[1] = ny / len; n[2] = nz / len;
-    return as_u(c.z);
+    return mat;
+}
+// resolve_normal as the cached packet kernels call it: the same normal, normalised by rm::unit_normal -- the short square root and
+// divisions when every lane of the wave that has a hit (the lanes that call it) is inside their window (bit-identical: ray_math.h),
+// the code above otherwise.  A variant of its own: the short sequences in resolve_normal itself raised the spills of
+// render_paths_pooled_kernel<4> (profiles/r04_notes.md), and no kernel but the cached packet kernels is to compile differently.
+__device__ __forceinline__ uint32_t resolve_normal_short(const DevScene& sc, uint32_t prim, float u, float v, float n[3]) {
+    float raw[3];
+    const uint32_t mat = raw_normal(sc, prim, u, v, raw);
+    rm::unit_normal(raw[0], raw[1], raw[2], n);
+    return mat;
 }
 
 // impl Object for Sphere::intersect, scene/primitives.rs:16-48 (lane-parallel; n = unit normal at the hit)

@@ -31,7 +31,7 @@
 #ifdef MP_PROF_MISSES  // profiling builds only (tools/build_variant.sh): slow-path calls of the mask cache, read by mp_prof_read
 namespace mp {
 namespace {
-__device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask builds [2] inner links followed [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk [7] pops skipped on an empty-mask leaf
+__device__ unsigned long long g_prof[10];  // [0] list builds [1] leaf-mask builds [2] inner links followed [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk [7] pops skipped on an empty-mask leaf [8] units that skip the per-ray scene pre-test [9] units that keep it
 }  // namespace
 }  // namespace mp
 #define MP_PROF_COUNT(i) do { if ((threadIdx.x & 63u) == 0u) atomicAdd(&g_prof[i], 1ull); } while (0)
@@ -41,6 +41,25 @@ __device__ unsigned long long g_prof[8];  // [0] list builds [1] leaf-mask build
 
 namespace mp {
 namespace {
+
+// Work the cached packet kernels (MCACHE = true) do once per unit instead of once per pass, each with a switch for A/B builds
+// (tools/build_variant.sh) that gives the per-pass code back: the sample key's part that is fixed per unit (-DMP_NO_KEY_HOIST), the scene
+// pre-test decided per unit (-DMP_NO_UNIT_PRETEST), and the shading normal's short normalisation (-DMP_NO_SHORT_NORMAL).
+#ifdef MP_NO_KEY_HOIST
+constexpr bool kKeyHoist = false;
+#else
+constexpr bool kKeyHoist = true;
+#endif
+#ifdef MP_NO_UNIT_PRETEST
+constexpr bool kUnitPretest = false;
+#else
+constexpr bool kUnitPretest = true;
+#endif
+#ifdef MP_NO_SHORT_NORMAL
+constexpr bool kShortNormal = false;
+#else
+constexpr bool kShortNormal = true;
+#endif
 
 // ---- fused tile render: Worker::render_tile (worker.rs:32-49) for a list of tiles -----------------------------
 struct RenderParams {
@@ -1037,10 +1056,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
         const size_t off = (static_cast<size_t>(tile_i) * ts * ts + static_cast<size_t>(py - T.min_y) * ts + (px - T.min_x)) * 4;
         float acc, cnt;  // pixel_sum (r=g=b) and alpha (worker.rs:40)
         pixel_state_load(P, off, inpix, sub == 0, acc, cnt);
+        // what the unit's passes share (kernels with a mask cache): whether they enter the walk without the per-ray scene pre-test
+        // (mask_cache_unit_reaches), and the lane's sample key at sample 0, to which a pass adds its sample index (ray_math.h,
+        // key_add_sample)
+        bool pre_skip = false;
+        uint64_t key0 = 0;
         if (MCACHE) {  // a new unit: other pixels, other bounds, set from the camera
             const RenderParams& C = params_view(KP);  // corner rays
             const uint32_t ux = T.min_x + (b % bx) * BW, uy = T.min_y + (b / bx) * BH;
+            if (kKeyHoist) key0 = sample_key(C.gen, px, py, 0u);
             mask_cache_begin_unit(mc, C.gen.s, C.gen.jitter_scale, ux, min(ux + BW, T.max_x) - 1u, uy, min(uy + BH, T.max_y) - 1u);
+            if (kUnitPretest && C.scene.has_pre) {
+                pre_skip = mask_cache_unit_reaches(mc, C.scene.pre_min, C.scene.pre_max);
+                if (pre_skip) MP_PROF_COUNT(8);
+                else MP_PROF_COUNT(9);
+            }
         }
         // passes are aligned to multiples of S in the absolute sample index, so that a chunk boundary (MP_FLAG_CHUNKED_SUM) never
         // falls inside a pass; lanes outside [s_begin, s_end) add +0.0, which is exact
@@ -1052,7 +1082,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
             r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.ix = r.iy = r.iz = 0.0f;
             {
                 const RenderParams& G = params_view(KP);  // ray generation
-                if (act) sample_ray(G.gen, px, py, s, r);
+                if (act) {
+                    if (MCACHE && kKeyHoist) sample_ray_keyed(G.gen, px, py, rm::key_add_sample(key0, s), r);
+                    else sample_ray(G.gen, px, py, s, r);
+                }
             }
             PacketHit h;
             h.t = FLT_MAX; h.u = h.v = 0.0f; h.prim = kNoPrim;
@@ -1072,7 +1105,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 #ifdef MP_PROF_NOWALK  // profiling builds only (tools/build_variant.sh): what a pass costs without its walk
                     const bool go = false;
 #else
-                    const bool go = act && W.scene.kind == 0u && may_hit_scene(W.scene, r);
+                    const bool go = act && W.scene.kind == 0u && ((MCACHE && kUnitPretest && pre_skip) || may_hit_scene(W.scene, r));
 #endif
                     if (__ballot(go) != 0) {
                         if (LDS_STACK) {
@@ -1094,6 +1127,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 #else
                 float nn[3];
                 if (OBJ) object_normal(H.scene, hinst, r, h.prim, h.u, h.v, nn);
+                else if (MCACHE && kShortNormal) resolve_normal_short(H.scene, h.prim, h.u, h.v, nn);
                 else resolve_normal(H.scene, h.prim, h.u, h.v, nn);
                 c = fabsf(r.dx * nn[0] + r.dy * nn[1] + r.dz * nn[2]);  // worker.rs:60
 #endif
@@ -1362,6 +1396,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
         if (__ballot(inpix) == 0) continue;
         const size_t off = (static_cast<size_t>(tile_i) * ts * ts + static_cast<size_t>(py - T.min_y) * ts + (px - T.min_x)) * 4;
         float cnt = 0.0f;  // alpha (worker.rs:40); the pixel's first lane is the one that stores it
+        uint64_t key0 = 0;  // (kernels with a mask cache) the lane's sample key at sample 0, as in render_tiles_packet_kernel
         {
             const AovParams& U = kernarg_view<AovParams>(KP);  // unit start: zeros, or the sums of the earlier passes
             float4* park = reinterpret_cast<float4*>(smem + (static_cast<size_t>(static_cast<int>(threadIdx.x) >> 6) * kParkPixels + pix) * U.park_pixel);
@@ -1378,6 +1413,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                 if (U.park_pixel > 32u) park[2] = a2;
             }
             if (MCACHE && lane == 0) mc.lds[kHdrState] = 0xFFFFFFFFu;  // a new unit: other pixels, other bounds
+            if (MCACHE && kKeyHoist) key0 = sample_key(U.r.gen, px, py, 0u);
             wave_lds_sync();
         }
         const uint32_t s_end = P.s_end;
@@ -1390,7 +1426,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
             {
                 const RenderParams& G = kernarg_view<AovParams>(KP).r;  // ray generation
                 act = inpix && s >= G.s_begin && s < s_end;
-                if (act) sample_ray(G.gen, px, py, s, r);
+                if (act) {
+                    if (MCACHE && kKeyHoist) sample_ray_keyed(G.gen, px, py, rm::key_add_sample(key0, s), r);
+                    else sample_ray(G.gen, px, py, s, r);
+                }
             }
             PacketHit h;
             h.t = FLT_MAX; h.u = h.v = 0.0f; h.prim = kNoPrim;
@@ -1425,7 +1464,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
             float nn[3] = {0.0f, 0.0f, 0.0f};
             uint32_t mat = 0u;
             if (hit) {
-                mat = OBJ ? object_normal(H.r.scene, hinst, r, h.prim, h.u, h.v, nn) : resolve_normal(H.r.scene, h.prim, h.u, h.v, nn);
+                mat = OBJ ? object_normal(H.r.scene, hinst, r, h.prim, h.u, h.v, nn)
+                    : (MCACHE && kShortNormal) ? resolve_normal_short(H.r.scene, h.prim, h.u, h.v, nn)
+                                               : resolve_normal(H.r.scene, h.prim, h.u, h.v, nn);
             } else if (H.r.scene.kind == 1u) {  // Scene<Sphere>: prim 0, material 0 (primitives.rs:40-46)
                 hit = act && sphere_intersect(H.r.scene, r, h.t, nn);
                 if (hit) h.prim = 0u;
@@ -2445,15 +2486,20 @@ int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixe
 }  // namespace mp
 
 #ifdef MP_PROF_MISSES
-extern "C" int mp_prof_read8(unsigned long long* out, int reset) {
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(mp::g_prof), sizeof(unsigned long long) * 8) != hipSuccess) return 1;
-    if (reset) { unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}; if (hipMemcpyToSymbol(HIP_SYMBOL(mp::g_prof), z, sizeof(z)) != hipSuccess) return 1; }
+// the first n counters (n <= 10: every slot of g_prof); reset != 0 zeroes all of them afterwards
+extern "C" int mp_prof_read_n(unsigned long long* out, int n, int reset) {
+    constexpr int kSlots = static_cast<int>(sizeof(mp::g_prof) / sizeof(mp::g_prof[0]));
+    if (n < 0 || n > kSlots) return 1;
+    unsigned long long all[kSlots] = {};
+    if (hipMemcpyFromSymbol(all, HIP_SYMBOL(mp::g_prof), sizeof(all)) != hipSuccess) return 1;
+    for (int i = 0; i < n; i++) out[i] = all[i];
+    if (reset) {
+        const unsigned long long z[kSlots] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(mp::g_prof), z, sizeof(z)) != hipSuccess) return 1;
+    }
     return 0;
 }
-extern "C" int mp_prof_read(unsigned long long* out, int reset) {  // the first four
-    unsigned long long all[8];
-    if (mp_prof_read8(all, reset) != 0) return 1;
-    for (int i = 0; i < 4; i++) out[i] = all[i];
-    return 0;
-}
+// (the entry points from before the counters grew: the first eight, the first four)
+extern "C" int mp_prof_read8(unsigned long long* out, int reset) { return mp_prof_read_n(out, 8, reset); }
+extern "C" int mp_prof_read(unsigned long long* out, int reset) { return mp_prof_read_n(out, 4, reset); }
 #endif

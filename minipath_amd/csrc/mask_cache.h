@@ -335,6 +335,38 @@ __device__ __forceinline__ bool bounds_may_hit(const float* b, const float bmn[3
     const float t1 = fmaxf(fmaxf(L[0], 0.0f), fmaxf(L[1], L[2])), t2 = fminf(U[0], fminf(U[1], U[2]));
     return !(t1 > t2);
 }
+// ---- the scene pre-test, decided once per unit ----------------------------------------------------------------------------------
+// may_hit_scene (group_walk.h) tests every ray of every pass against the union box of the root's children.  Called by every lane
+// after mask_cache_begin_unit: if the unit adopted bounds B from its corner rays, the box {pre_min, pre_max} is put to
+// bounds_may_hit's corner evaluation under B's sign pattern (read from the header: a run-time OCT, otherwise the same arithmetic;
+// no upper limit on t2, which only errs towards "may").  True: some ray inside B may reach the box -- in an interior frame every
+// ray does -- and the unit's passes enter the walk without the per-ray test.  False (no B, or B cannot reach the box): the caller
+// keeps the per-ray test, which for rays inside such a B fails for every ray and skips the walk.
+//   The answer steers work only, never a result, whatever B later becomes (a pass that widens B keeps "may" true, the union
+// containing the old B; a pass of another sign pattern replaces B, and the unit goes on without the per-ray test).  Skipping the
+// pre-test is exact by the argument above may_hit_scene: a ray whose interval against the union box U is empty passes the slab
+// test of no child box of the root, each being inside U with its interval inside U's in floating point too.  The cached walk
+// starts from the root's unit list, whose every entry is such a child or a descendant nested in one (absorbed under
+// unit_list_build's rule, or collapsed into the record by device_tree.cpp's, both of which require the nesting on the floats the
+// walk loads), so its interval is inside U's as well: the ray is live in no frame, tests no triangle and leaves the walk as a
+// miss, as the skipped walk would have left it.  The uncached walks a pass may fall back to open the root's children with the
+// same slab test.  (Scenes without a pre-test box, has_pre == 0, run every ray through the walks in just this way.)
+__device__ __forceinline__ bool mask_cache_unit_reaches(const MaskCache& mc, const float pre_min[3], const float pre_max[3]) {
+    const uint32_t state = __builtin_amdgcn_readfirstlane(mc.lds[kHdrState]);
+    if (state == 0xFFFFFFFFu) return false;
+    const float* b = reinterpret_cast<const float*>(mc.lds);
+    float L[3], U[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const float y = pre_min[k] - b[3 + k], z = pre_max[k] - b[k];
+        const bool neg = ((state >> k) & 1u) != 0u;
+        const float lo_src = neg ? z : y, hi_src = neg ? y : z;
+        L[k] = fminf(lo_src * b[6 + k], lo_src * b[9 + k]);
+        U[k] = fmaxf(hi_src * b[6 + k], hi_src * b[9 + k]);
+    }
+    const float t1 = fmaxf(fmaxf(L[0], 0.0f), fmaxf(L[1], L[2])), t2 = fminf(U[0], fminf(U[1], U[2]));
+    return __ballot(!(t1 > t2)) != 0;  // (the same value in every lane: a scalar for the caller)
+}
 
 // ---- per-unit child LISTS: the kept children of a node, with kept descendants in place of the children that need no test --------
 // Counted (tools/unit_list_count.py, profiles/unit_lists_notes.md): under a unit's masks a node keeps 1.43 children, so the walk

@@ -1,7 +1,7 @@
-// libmp_probe.so: test probes of ray_math.h on the GPU (tests/test_ray_math_gpu.py), built with the library's flags.  Each entry
+// libmp_probe.so: test probes of ray_math.h on the GPU (tests/test_ray_math_gpu.py, tests/test_short_normal_gpu.py), built with the library's flags.  Each entry
 // point launches kernels that compare a short sequence of ray_math.h with the compiler's `/` / sqrtf bit for bit and returns
 // counters: out[0] = mismatches, out[1] = cases compared, out[2] = smallest mismatching case index (~0 if none), out[3] = waves
-// that took the short path (ray probe).  The kernels write nothing but these four counters.  The return value is 0 or the HIP error
+// that took the short path (ray and normal probes).  The kernels write nothing but these four counters.  The return value is 0 or the HIP error
 // code of the first call that failed.
 #include <hip/hip_runtime.h>
 
@@ -110,6 +110,48 @@ __global__ void ray_kernel(uint64_t seed, int mode, unsigned long long* out) {
     }
 }
 
+// one shading normal per lane, as resolve_normal_short hands it to unit_normal; mode 0: components of magnitude 2^-40 .. 2^38 (every
+// wave short); mode 1: as 0 with components replaced by +0 or -0, one in three each, but never all three of a lane (walls along
+// the axes: every wave short); mode 2: as 1, but in every odd wave one lane carries a denormal, tiny, huge, infinite or NaN
+// component or is zero in all three (those waves fall back); mode 3: components of random bits.  unit_normal against sqrtf and
+// the three `/`, all three outputs.
+__global__ void normal_kernel(uint64_t seed, int mode, unsigned long long* out) {
+    const uint64_t idx = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint64_t wave = idx >> 6;
+    const int lane = static_cast<int>(idx & 63);
+    float d[3];
+    for (int c = 0; c < 3; c++) {
+        const uint64_t h = mix64(seed ^ (idx * 4 + c));
+        d[c] = mode == 3 ? __uint_as_float(static_cast<uint32_t>(h)) : pick(h, 127 - 40, 127 + 38);
+    }
+    if (mode == 1 || mode == 2) {
+        const uint64_t z = mix64(seed ^ (idx * 4 + 3));
+        const uint32_t keep = static_cast<uint32_t>(z >> 32) % 3u;  // this component stays as it is
+        for (int c = 0; c < 3; c++) {
+            const uint32_t sel = static_cast<uint32_t>(z >> (8 * c)) % 3u;  // 0: +0, 1: -0, 2: unchanged
+            if (static_cast<uint32_t>(c) != keep && sel != 2u) d[c] = sel == 0u ? 0.0f : -0.0f;
+        }
+    }
+    if (mode == 2 && (wave & 1u) && lane == static_cast<int>(mix64(seed ^ wave) & 63u)) {
+        // denormal, tiny, tiny negative, huge, +inf, -inf, NaN in one component; or all three zero (selected, not indexed: no private array)
+        const uint32_t k = static_cast<uint32_t>(wave >> 1) & 7u;
+        const float v = k == 0 ? 0x1p-140f : k == 1 ? 0x1p-41f : k == 2 ? -0x1p-100f : k == 3 ? 0x1p45f : k == 4 ? __builtin_inff()
+                      : k == 5 ? -__builtin_inff() : __builtin_nanf("");
+        const int c = static_cast<int>((wave >> 4) % 3);
+        if (k == 7u) { d[0] = 0.0f; d[1] = -0.0f; d[2] = 0.0f; }
+        else if (c == 0) d[0] = v; else if (c == 1) d[1] = v; else d[2] = v;
+    }
+    float n[3];
+    const bool fast = unit_normal(d[0], d[1], d[2], n);
+    const float len = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const bool bad = differ(n[0], d[0] / len) || differ(n[1], d[1] / len) || differ(n[2], d[2] / len);
+    record(out, bad, idx);
+    if (lane == 0) {
+        atomicAdd(out + 1, 64ull);
+        if (fast) atomicAdd(out + 3, 1ull);
+    }
+}
+
 // One launch on a fresh counter buffer.  HIP's last-error state is per thread and sticky: an error that earlier work of the process
 // left there (any library, any earlier call whose status nobody read) is not this probe's, so it is cleared before the launch, and
 // every call's own status is checked.
@@ -177,5 +219,10 @@ int mp_probe_div(uint64_t seed, uint64_t blocks, unsigned long long* out) {
 int mp_probe_ray(uint64_t seed, int mode, uint64_t blocks, unsigned long long* out) {
     g_seed = seed; g_mode = mode; g_blocks = blocks;
     return run([](unsigned long long* d) { hipLaunchKernelGGL(ray_kernel, dim3(static_cast<uint32_t>(g_blocks)), dim3(256), 0, 0, g_seed, g_mode, d); }, out);
+}
+// blocks x 256 shading normals
+int mp_probe_normal(uint64_t seed, int mode, uint64_t blocks, unsigned long long* out) {
+    g_seed = seed; g_mode = mode; g_blocks = blocks;
+    return run([](unsigned long long* d) { hipLaunchKernelGGL(normal_kernel, dim3(static_cast<uint32_t>(g_blocks)), dim3(256), 0, 0, g_seed, g_mode, d); }, out);
 }
 }

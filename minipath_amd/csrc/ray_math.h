@@ -128,6 +128,18 @@ MP_RM_FN void unit_disc(Rng& rng, float& x1, float& x2) {
     }
 }
 
+// ---- the sample key, per pass from the pixel's key at sample 0 --------------------------------------------------------------
+// key = seed + ((y * width + x) * spp + s), every operation in u64 mod 2^64 (include/minipath_hip.h "Seeded mode"; sample_key,
+// wave_common.h).  Only s changes between the passes of a work unit, and sums associate mod 2^64, so
+//     key(x, y, s) = key(x, y, 0) + s
+// for every seed, image and sample index, wraps of the low word and of the whole sum included: a kernel whose lane keeps its pixel
+// for a unit computes key(x, y, 0) once per unit and adds s per pass -- one add with carry (v_add_co_u32 + v_addc_co_u32) in place
+// of three 64-bit multiply-adds.
+MP_RM_FN uint64_t sample_key_u64(uint64_t seed, uint32_t width, uint32_t spp, uint32_t x, uint32_t y, uint32_t s) {
+    return seed + ((static_cast<uint64_t>(y) * width + x) * spp + s);
+}
+MP_RM_FN uint64_t key_add_sample(uint64_t key0, uint32_t s) { return u64_join(add64(u64_split(key0), U64{s, 0u})); }
+
 #if defined(__HIPCC__)
 // ---- IEEE f32 division and sqrt without their range fix-ups ------------------------------------------------------------
 // With f32 denormals enabled (the build's -fno-gpu-flush-denormals-to-zero), `a / b` compiles to
@@ -197,6 +209,39 @@ __device__ __forceinline__ bool ray_dir(float dx, float dy, float dz, float& ux,
     ix = (ux == 0.0f) ? __builtin_inff() : 1.0f / ux;
     iy = (uy == 0.0f) ? __builtin_inff() : 1.0f / uy;
     iz = (uz == 0.0f) ? __builtin_inff() : 1.0f / uz;
+    return false;
+}
+
+// A shading normal's normalisation (resolve_normal, group_walk.h): n = (nx, ny, nz) / sqrtf(nx^2 + ny^2 + nz^2).  Returns whether the
+// wave took the short sequences.  Unlike a ray's direction a normal often has components that are zero, of either sign (a wall along
+// an axis: the cross product's x * 0 - y * 0 is +0 or -0 by the signs of x and y), so the numerators admitted are
+//     a = +-0   or   |a| in [2^-40, 2^41)      (W0)
+// with the divisor as in (W): the sum x in [2^-80, 2^80), so len = sqrt_short(x) in [2^-40, 2^40] and positive; the bound |a| < 2^41
+// is the window's argument above (trivial for a zero).  Non-zero numerators: (W) holds, div_short is a / len, and since len > 0 the
+// quotient carries a's sign already.  Zero numerators: V_DIV_SCALE returns NaN for both scalings, and V_DIV_FIXUP, whose first test
+// after the NaNs is the zero numerator over a non-zero finite divisor, returns a zero with the sign sign(a) ^ sign(len) = sign(a):
+// a / len is a itself.  div_short gives +0 for either zero (the division's note above; with y > 0, a = +0: q = +0, r = (-0) + (+0)
+// = +0, and every later sum is (+0) + (+0); a = -0: q = -0, r = (+0) + (-0) = +0, q = (+0) + (-0) = +0, r = (-0) + (-0) = -0, and
+// the last sum is (-0) + (+0) = +0), so copying a's sign onto the short quotient (one v_bfi_b32) is the identity for a non-zero
+// numerator and makes a zero one right.  A component that is neither -- non-zero below 2^-40, where the quotient may be denormal and V_DIV_SCALE rescales -- sends
+// the whole wave to the plain code, like a sum outside its window (a NaN or infinite component, or all three zero).
+//   The admission test on the bits: with the sign shifted out, m = bits << 1 is 0 for +-0 and monotone in |a| otherwise, so
+// m - 1 (mod 2^32) >= (bits(2^-40) << 1) - 1  <=>  a = +-0 or |a| >= 2^-40 (a NaN passes here and fails the window of the sum).
+__device__ __forceinline__ bool unit_normal(float nx, float ny, float nz, float n[3]) {
+    const float x = nx * nx + ny * ny + nz * nz;
+    constexpr uint32_t kLo2 = (0x2B800000u << 1) - 1u;  // 0x2B800000 = 2^-40
+    static_assert(kCompLo == 0x1p-40f, "kLo2 is kCompLo's bit pattern, shifted");
+    const uint32_t mx = (__float_as_uint(nx) << 1) - 1u, my = (__float_as_uint(ny) << 1) - 1u, mz = (__float_as_uint(nz) << 1) - 1u;
+    const bool ok = sum_in_window(x) && min(min(mx, my), mz) >= kLo2;
+    if (__ballot(!ok) == 0) {
+        const float len = sqrt_short(x), y = div_rcp(len);
+        n[0] = __builtin_copysignf(div_short(nx, len, y), nx);
+        n[1] = __builtin_copysignf(div_short(ny, len, y), ny);
+        n[2] = __builtin_copysignf(div_short(nz, len, y), nz);
+        return true;
+    }
+    const float len = sqrtf(x);
+    n[0] = nx / len; n[1] = ny / len; n[2] = nz / len;
     return false;
 }
 

@@ -91,13 +91,20 @@ __device__ __forceinline__ void sample_ray_rng(const RayGen& P, uint32_t x, uint
 
 // key = mix(seed) + sample index; `P.seed` already holds mix(seed) (mixed_seed(), on the host)
 __device__ __forceinline__ uint64_t sample_key(const RayGen& P, uint32_t x, uint32_t y, uint32_t sample) {
-    return P.seed + ((static_cast<uint64_t>(y) * P.width + x) * P.spp + sample);
+    return rm::sample_key_u64(P.seed, P.width, P.spp, x, y, sample);
 }
 
 // seeded per (pixel, sample): include/minipath_hip.h "Seeded mode"
 __device__ __forceinline__ void sample_ray(const RayGen& P, uint32_t x, uint32_t y, uint32_t sample, Ray& r) {
     Rng rng;
     rng_seed(rng, sample_key(P, x, y, sample));
+    sample_ray_rng<false>(P, x, y, rng, r);
+}
+// ... with the key handed in: the cached packet kernels form it per pass as sample_key(P, x, y, 0), computed once per work unit,
+// plus the sample index (rm::key_add_sample, ray_math.h), which is the same integer as sample_key(P, x, y, sample)
+__device__ __forceinline__ void sample_ray_keyed(const RayGen& P, uint32_t x, uint32_t y, uint64_t key, Ray& r) {
+    Rng rng;
+    rng_seed(rng, key);
     sample_ray_rng<false>(P, x, y, rng, r);
 }
 
