@@ -8,7 +8,7 @@
 //     a chain of 2-child nodes 23 levels deep that a ray crosses 10 times), and each node step costs a walk the same whether
 //     the node has two children or eight;
 //   * the PACKET tree: the same absorption (rule, policy and order) carried on to SIXTEEN slots per node, for the cached packet
-//     walk alone (kernels.hip, trace_packet_cached).  That walk tests a child when it is popped and only the children its per-unit
+//     walk alone (packet_walk.h, trace_packet_cached).  That walk tests a child when it is popped and only the children its per-unit
 //     mask lets through, so a masked-off child of a wider node costs nothing per pass and fewer, wider nodes mean fewer node
 //     steps (counted: tools/packet_tree_count.py, profiles/packet_tree_notes.md: 22.6 % fewer pops and 30.6 % fewer node visits
 //     on the stand-in).  A node is 16 records of 32 bytes; unused slots are null links behind the last real child.  The walk's
@@ -104,7 +104,7 @@ uint32_t stack_bound(const std::vector<float>& nodes, uint32_t slots, uint32_t c
     return std::max<uint32_t>(1u, bound[root >> 6]);
 }
 
-// Exact bound of the cached packet walk's FRAME stack (kernels.hip, RegStack3): a frame goes to the stack when a child opens a
+// Exact bound of the cached packet walk's FRAME stack (packet_walk.h, RegStack3): a frame goes to the stack when a child opens a
 // frame of its own while lower siblings still wait.  frames(node) = max over inner children at position p of
 // (p > 0) + frames(child).  Never above the literal tree's stack_bound: every stacked frame holds a waiting child, which waits in
 // the reference's stack too, and distinct frames are distinct reference nodes.
@@ -194,7 +194,7 @@ int build_device_tree(const HostBvh& h, const std::vector<uint32_t>& pkt_valid, 
     }
     // wide / packet tree, numbered in pre-order (a node's first subtree follows it: the order the walks touch memory in)
     // The first record of the tail padding (slot count * slots) is the ROOT's: an unbounded box and the root's link, so that a walk
-    // which tests an entry's box when it pops the entry (kernels.hip, trace_packet_cached) needs no special case for the root --
+    // which tests an entry's box when it pops the entry (packet_walk.h, trace_packet_cached) needs no special case for the root --
     // every ray passes an unbounded box with t1 = 0, which is what "the root is never culled" (:28-32) means.
     auto put_root_record = [&]() {
         float* rr = &out.nodes[static_cast<size_t>(out.count) * stride];

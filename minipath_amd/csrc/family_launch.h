@@ -20,10 +20,25 @@ namespace mp {
 int check(hipError_t e, const char* what, std::string& err);
 void note_launch(KernelId id);
 int launched(KernelId id, std::string& err);
+// The families' units fill their kernels' parameters from an accepted plan and launch: kernels_tiles.hip and kernels_paths.hip
+// (behind launch_render_tiles: without and with a path extension), kernels_aov.hip (launch_render_aov), kernels_staged.hip
+// (launch_render_paths_wavefront, with its workspace and its batch / chunk / depth loops)
+int launch_tiles(const RenderLaunch& L, const LaunchPlan& plan, hipStream_t st, std::string& err);
+int launch_paths(const RenderLaunch& L, const LaunchPlan& plan, hipStream_t st, std::string& err);
+int launch_aov(const RenderLaunch& L, const mp_aov_planes_ex& planes, const LaunchPlan& plan, hipStream_t st, std::string& err);
+int launch_staged(const RenderLaunch& L, const WavefrontPlan& plan, hipStream_t st, std::string& err);
 // kernels_queries.hip: the three ray queries (plan, fill, launch) behind launch_trace_rays and launch_query_rays
 int launch_rays(QueryKind kind, const DevScene& sc, const float* ox, const float* oy, const float* oz, const float* dx, const float* dy,
                 const float* dz, const float* tmax, uint64_t n, const mp_hits_soa* hits, uint8_t* occluded, int cu_count, void* stream,
                 std::string& err);
+#ifdef MP_PROF_MISSES
+// counted builds (prof_counters.h): each unit that runs the cached packet walk adds its copy of the counters to sum[0 .. kProfSlots)
+// and, with reset != 0, zeroes it; mp_prof_read* (kernels.hip) report the sum
+constexpr int kProfSlots = 10;
+int prof_add_tiles(unsigned long long* sum, int reset);
+int prof_add_aov(unsigned long long* sum, int reset);
+int prof_add_paths(unsigned long long* sum, int reset);
+#endif
 #pragma GCC visibility pop
 
 // The statement that launches is the statement that records (note_launch, kernels.hip): there is no second selection to keep in step.

@@ -392,7 +392,7 @@ int upload_scene(mp_scene* s) {
     for (size_t p = 0; p < np; p++)
         for (int i = 0; i < 8; i++)
             for (int k = 0; k < 9; k++) tris_aos[(p * 8 + i) * kTriDwords + k] = tris[p * kPacketDwords + k * 8 + i];
-    // magnitude bound behind the packet walk's triangle masks (kernels.hip, tri_may_hit): no overflow in the interval evaluation
+    // magnitude bound behind the packet walk's triangle masks (mask_cache.h, tri_may_hit; packet_walk.h, leaf_mask_slow): no overflow in the interval evaluation
     s->dev.tris_bounded = 1u;
     for (size_t i = 0; i < np * 8 && s->dev.tris_bounded; i++)
         for (int k = 0; k < 9; k++) {

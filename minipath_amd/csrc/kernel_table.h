@@ -1,8 +1,8 @@
 // Every kernel instantiation libminipath_hip.so can launch, written down once, as one sub-table per kernel family.  The list
 // generates the ids the launch plans (launch_plan.h) return, the names mp_ctx_last_kernels reports -- the kernel with its template
 // arguments as the row writes them -- and the switch that records the name and launches (family_launch.h), which every translation
-// unit expands over the sub-tables of its own kernels: kernels_queries.hip over the ray queries, kernels.hip over the others until
-// they move into units of their own.  No HIP header: the planning source includes it too.
+// unit expands over the sub-table of its own family (the unit's name stands above each).  No HIP header: the planning source
+// includes it too.
 //
 // A row is X(id, kernel).  MP_KERNEL_TABLE is the sub-tables in the order the ids have always had.  Templates stand in the order the
 // launchers have always named them: the compiler emits device code in the order of first use, so moving a row moves its kernel
@@ -14,6 +14,7 @@
 #endif
 
 // clang-format off
+// kernels_paths.hip
 #define MP_KERNELS_PATHS(X)                                                                         \
     /* path extension: pooled <NSUB>, then <S, OBJ, RGB[, MCACHE]> */                               \
     X(K_PATHS_POOLED_4,        render_paths_pooled_kernel<4>)                                       \
@@ -37,6 +38,7 @@
     X(K_PATHS_1_RGB,           render_paths_kernel<1, false, true>)                                 \
     X(K_PATHS_1_GREY,          render_paths_kernel<1, false, false>)
 
+// kernels_tiles.hip
 #define MP_KERNELS_TILES(X)                                                                         \
     /* 8-lane groups <S, OBJ>, two rays per lane <W> */                                             \
     X(K_GROUPS_OBJ,            render_tiles_kernel<1, true>)                                        \
@@ -71,6 +73,7 @@
     X(K_PACKET_1,              render_tiles_packet_kernel<1, false, 7>)                             \
     /* (end of the fused tiles) */
 
+// kernels_aov.hip
 #define MP_KERNELS_AOV(X)                                                                           \
     /* feature planes <S, LDS_STACK, W[, OBJ[, MCACHE]]> */                                         \
     X(K_AOV_16_CACHED,         render_aov_packet_kernel<16, false, 8, false, true>)                 \
@@ -85,6 +88,7 @@
     X(K_AOV_4,                 render_aov_packet_kernel<4, false, 8>)                               \
     X(K_AOV_1,                 render_aov_packet_kernel<1, false, 8>)
 
+// kernels_staged.hip
 #define MP_KERNELS_STAGED(X)                                                                        \
     /* staged path evaluation: camera <LDS_STACK, OBJ>, vertex <NCHAN, OBJ>, trace <OBJ> */         \
     X(K_WF_CAMERA_LDS_OBJ,     wf_camera_kernel<true, true>)                                        \
@@ -111,6 +115,7 @@
     X(K_QUERY_BOUNDED_OBJ,     query_rays_kernel<true, kBounded>)                                   \
     X(K_QUERY_BOUNDED,         query_rays_kernel<false, kBounded>)
 
+// kernels.hip
 #define MP_KERNELS_UTILITIES(X)                                                                     \
     /* utilities */                                                                                 \
     X(K_SET_U64,               set_u64_kernel)                                                      \

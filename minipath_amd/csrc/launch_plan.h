@@ -1,4 +1,4 @@
-// Launch plans: everything a launcher of kernels.hip decides and sizes before it touches the GPU -- the instantiation (an id of
+// Launch plans: everything a launcher (kernels.hip and the families' units) decides and sizes before it touches the GPU -- the instantiation (an id of
 // kernel_table.h), grid, dynamic LDS, lds_per_wave, pool and batch geometry, or the refusal.  Pure host code without a HIP header:
 // the rules are tested on any machine through libmp_plan_probe.so (tests/test_launch_plan_cpu.py).
 #pragma once
@@ -7,12 +7,12 @@
 #include "mp_internal.h"
 
 #ifndef MP_PATHS_WPE
-#define MP_PATHS_WPE 6  // as kernels.hip: waves per SIMD the path kernel's registers are held to
+#define MP_PATHS_WPE 6  // waves per SIMD the path kernel's registers are held to (kernels_paths.hip; A/B-measured, profiles/r03_notes.md)
 #endif
 
 namespace mp {
 
-// Sizes of the device code the plans depend on; kernels.hip asserts each against the device's own constant.
+// Sizes of the device code the plans depend on; the header or unit that defines the device's own constant asserts each against it.
 constexpr uint32_t kPlanQueueFloats = 6 * 64;       // kQueueFloats
 constexpr uint32_t kPlanMaskCacheDwords = 928;      // mc::kMaskCacheDwords: 3 712 bytes per wave
 constexpr uint32_t kPlanDirBins = 512;              // kDirBins

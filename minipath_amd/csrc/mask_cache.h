@@ -1,4 +1,4 @@
-// The packet walk's per-work-unit mask cache (kernels.hip, trace_packet_cached): the bounds B of a unit's rays, the predicates that
+// The packet walk's per-work-unit mask cache (packet_walk.h, trace_packet_cached): the bounds B of a unit's rays, the predicates that
 // prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
 // that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
 // per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define

@@ -280,7 +280,7 @@ __global__ void exit_kernel(uint64_t seed, uint64_t base, uint64_t ncases, unsig
     const uint64_t hl = hsh(seed, c, 90);
     const uint64_t live_mask = (hl & 7u) == 0u ? ~0ull : (hsh(seed, c, 91) | (1ull << (hl >> 58)));
     const bool live = ((live_mask >> lane) & 1u) != 0u;
-    // the walk's sequence up to the division (kernels.hip, trace_packet_cached)
+    // the walk's sequence up to the division (packet_walk.h, trace_packet_cached)
     const float dx = x[3], dy = x[4], dz = x[5];
     const float hx = fms(dy, e2[2], dz * e2[1]), hy = fms(dz, e2[0], dx * e2[2]), hz = fms(dx, e2[1], dy * e2[0]);
     const float det = fma_dot(e1[0], e1[1], e1[2], hx, hy, hz);

@@ -166,7 +166,7 @@ constexpr int kTriDwords = 9;      // device triangle record: v0.xyz, e1.xyz, e2
 constexpr int kNodeDwords = 56;    // host staging rows: minx..maxz (8 floats each) + link[8]
 constexpr int kPacketDwords = 72;  // host staging rows: v0.xyz, e1.xyz, e2.xyz (8 floats each)
 
-// ---- kernel launchers (kernels.hip; the ray queries' half: kernels_queries.hip) ---------------------------------------------------------------------
+// ---- kernel launchers (kernels.hip; each hands its plan to the family's unit, kernels_*.hip) ---------------------------------------------------------------------
 struct RenderLaunch {
     DevScene scene;
     mp_camera_sampler sampler;
@@ -218,9 +218,9 @@ int launch_untile(uint32_t width, uint32_t height, uint32_t tile_size, const mp_
 
 int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixels, void* stream, std::string& err);
 
-// The launchers above decide nothing themselves: each asks its plan (launch_plan.h: kernel id, grid, LDS, refusals), fills the
-// kernel's parameters and launches the id through the one switch over kernel_table.h (family_launch.h), which every translation
-// unit expands over the rows of its own kernels.
+// The launchers above decide nothing themselves: each asks its plan (launch_plan.h: kernel id, grid, LDS, refusals) and returns the
+// refusal, or hands the plan to the family's unit, which fills the kernel's parameters and launches the id through the one switch
+// over kernel_table.h (family_launch.h), which every translation unit expands over the rows of its own kernels.
 // Launch record (mp_ctx_last_kernels): that switch notes every kernel it launches in a list of the calling thread.
 // launch_log_clear() empties it; launch_log_text() gives the distinct names (the table's) since then, in launch order, one per line.
 void launch_log_clear();

@@ -1,5 +1,5 @@
 // Device code every kernel family of libminipath_hip.so shares: small wave helpers, the 8-lane-group collectives on DPP, the RNG
-// and camera ray generation (RayGen, sample_ray).  Like every device header of the library it keeps its code in the anonymous
+// and camera ray generation (RayGen with the host code that fills it, sample_ray).  Like every device header of the library it keeps its code in the anonymous
 // namespace inside mp: each family's translation unit compiles its own copy, and no device function is called across units.
 #pragma once
 
@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "launch_plan.h"
 #include "mask_cache.h"
 #include "mp_internal.h"
 #include "ray_math.h"
@@ -21,6 +22,7 @@ using namespace mc;
 
 constexpr uint32_t kNoPrim = 0xFFFFFFFFu;
 constexpr int kQueueFloats = 6 * 64;  // ox,oy,oz,dx,dy,dz (unit direction) x 64 slots ; hit (t,prim,u,v) aliases rows 0..3
+static_assert(kPlanQueueFloats == kQueueFloats, "launch_plan.h sizes the launches with the device code's constants");
 
 // set bits of a wave mask below this lane (v_mbcnt: no per-lane mask register to keep)
 __device__ __forceinline__ int rank_below(uint64_t m) {
@@ -76,6 +78,41 @@ struct RayGen {
     uint64_t seed;  // mix(settings.seed), see mixed_seed()
 };
 
+// ---- host side: filling RayGen ------------------------------------------------------------------------------------
+// UniformFloat::new_inclusive(low, high).scale (rand 0.9): (high-low)/max_rand, reduced by ulps until
+// scale*max_rand + low <= high
+float uniform_inclusive_scale(float low, float high) {
+    const float max_rand = 1.0f - FLT_EPSILON;
+    float scale = (high - low) / max_rand;
+    for (;;) {
+        volatile float top = scale * max_rand;
+        top = top + low;
+        if (!(top > high)) break;
+        uint32_t b;
+        __builtin_memcpy(&b, &scale, 4);
+        b -= 1;
+        __builtin_memcpy(&scale, &b, 4);
+    }
+    return scale;
+}
+
+// Seeded mode (include/minipath_hip.h): the first SplitMix64 output for state `seed`, so that consecutive seeds give unrelated
+// sample streams; the per-sample index is added on the device (sample_key).
+uint64_t mixed_seed(uint64_t seed) {
+    uint64_t z = seed + 0x9e3779b97f4a7c15ull;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return z ^ (z >> 31);
+}
+
+void fill_raygen(RayGen& G, const mp_camera_sampler& s, uint32_t width, uint32_t spp, uint64_t seed) {
+    G.s = s;
+    G.jitter_scale = uniform_inclusive_scale(-0.5f, 0.5f);
+    G.width = width;
+    G.spp = spp;
+    G.seed = mixed_seed(seed);
+}
+
 // CameraSampler::sample_ray camera.rs:176-191 on an already seeded stream (ADVANCE = false: nothing is drawn from it afterwards);
 // ray_new and the arithmetic from the film point on are camera_rays.h's (camera_film, camera_lens_ray): the mask cache's corner rays share it
 template <bool ADVANCE = true>
@@ -109,7 +146,7 @@ __device__ __forceinline__ void sample_ray_keyed(const RayGen& P, uint32_t x, ui
 }
 
 // A short-lived view of a kernel's arguments through the kernarg segment pointer: the compiler barrier on the pointer ends the
-// life of everything loaded through the previous view (why: kernels.hip, above params_view).
+// life of everything loaded through the previous view (why: render_state.h, above params_view).
 template <class T>
 __device__ __forceinline__ const T& kernarg_view(const __attribute__((address_space(4))) T* kp) {
     asm volatile("" : "+s"(kp));

@@ -120,7 +120,7 @@ def unit_hit_packets(oracle, orc, sampler, res, spp, seed, unit, rays_per_pixel)
 # scenes.atrium(1, 0.5): 1 398 literal, 1 388 wide and 1 027 packet-tree nodes, 18 326 packets -- both walked trees exceed the node
 # table, the leaves the leaf table many times over; the benchmark's interior view on a small frame.
 EVICT_DETAIL, EVICT_RES, EVICT_TS, EVICT_SEED = 0.5, (96, 64), 32, 5
-# kernel family -> (samples per pixel, the kernel's unit in pixels (kernels.hip: BW x BH for the samples in flight), sampled rays per pixel)
+# kernel family -> (samples per pixel, the kernel's unit in pixels (the family's unit, kernels_*.hip: BW x BH for the samples in flight), sampled rays per pixel)
 EVICT_FAMILIES = {
     "packet, 16 in flight": (64, (2, 2), 8),
     "packet, 4 in flight": (16, (4, 4), 4),

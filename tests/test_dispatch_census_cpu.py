@@ -85,14 +85,17 @@ def test_the_subtables_are_the_table_and_every_unit_launches_its_own():
     ids = [i for i, _ in rows]
     assert len(ids) == len(set(ids)), "... with each row once"
     assert [k.replace("MP_MCACHE_WPE", "8") for _, k in rows] == pp.table(), "... and it is the table the library was built from, in its order"
-    # every translation unit expands the switch once: over a sub-table, or over a concatenation of sub-tables that it defines itself
+    # every translation unit expands the switch once, over the sub-table of its own family
     src = _library_sources()
     units = {}
     for f, t in src.items():
         for name in re.findall(r"^MP_FAMILY_LAUNCHER\((\w+)\)", t, flags=re.M):
-            assert f.endswith(".hip") and f not in units, (f, name)
-            units[f] = [name] if name in subs else re.findall(r"(MP_KERNELS_\w+)\(X\)", re.search(r"#define %s\(X\)([^\n]*)\n" % name, t).group(1))
-    assert len(units) >= 2 and units["kernels_queries.hip"] == ["MP_KERNELS_QUERIES"]
+            assert f.endswith(".hip") and f not in units and name in subs, (f, name)
+            units[f] = [name]
+    assert units == {"kernels.hip": ["MP_KERNELS_UTILITIES"], "kernels_tiles.hip": ["MP_KERNELS_TILES"], "kernels_aov.hip": ["MP_KERNELS_AOV"],
+                     "kernels_paths.hip": ["MP_KERNELS_PATHS"], "kernels_staged.hip": ["MP_KERNELS_STAGED"],
+                     "kernels_queries.hip": ["MP_KERNELS_QUERIES"]}
+    assert not [f for f, t in src.items() if "MP_KERNELS_HERE" in t], "no unit concatenates sub-tables of its own any more"
     # ... every sub-table is expanded exactly once in the library
     assert sorted(n for names in units.values() for n in names) == sorted(subs), units
     # ... by the unit that defines the sub-table's kernels, which defines no others

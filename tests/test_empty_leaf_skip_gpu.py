@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the cached packet walk's skip of list entries whose leaf has an empty unit triangle mask (kernels.hip,
+"""GPU tests (-m gpu) of the cached packet walk's skip of list entries whose leaf has an empty unit triangle mask (packet_walk.h,
 trace_packet_cached: the visit that finds the mask empty marks the arena entry, later pops of the entry stop at the mark).
 
 Frames against the oracle's bits, with the kernels named, in units of four passes -- the fewest the plans give a cached kernel

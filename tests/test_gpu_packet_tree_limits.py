@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the cached packet walk (kernels.hip, trace_packet_cached<OCT, MB>) where its two word formats can go
+"""GPU tests (-m gpu) of the cached packet walk (packet_walk.h, trace_packet_cached) where its two word formats can go
 wrong without a small scene noticing.  Helpers and constructions: tests/graft_model.py; the premises are asserted on the CPU too
 (tests/test_packet_tree_limits_cpu.py).
 

@@ -1,4 +1,4 @@
-"""The argument behind the packet walk's triangle masks (kernels.hip, tri_may_hit), checked on the CPU: the Moeller-Trumbore
+"""The argument behind the packet walk's triangle masks (mask_cache.h, tri_may_hit), checked on the CPU: the Moeller-Trumbore
 expression sequence evaluated on intervals (corner evaluation of monotone f32 operations) never rejects a triangle that some ray
 inside the bounds hits.  numpy model of tools/sim_tri_reject.py against per-ray f32 tests on camera packets of the teapot."""
 import os
@@ -32,7 +32,7 @@ def test_interval_rejection_is_conservative():
 
 
 def test_interval_rejection_of_child_boxes_is_conservative():
-    """... and the node masks (kernels.hip, bounds_may_hit): a child box the bounds reject is passed by no ray inside them."""
+    """... and the node masks (mask_cache.h, bounds_may_hit): a child box the bounds reject is passed by no ray inside them."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import sim_tri_reject as st
     from sim_collapse import RefTree, build_device, load, slab

@@ -46,10 +46,11 @@ def _device_sources():
 
 def test_kernels_take_predicates_from_header():
     sources = _device_sources()
-    assert {"kernels.hip", "kernels_queries.hip", "group_walk.h", "wave_common.h"} <= set(sources)
+    assert {"kernels.hip", "kernels_tiles.hip", "kernels_aov.hip", "kernels_paths.hip", "kernels_staged.hip", "kernels_queries.hip",
+            "group_walk.h", "wave_common.h", "render_state.h", "packet_walk.h", "path_shading.h", "prof_counters.h"} <= set(sources)
     header = open(os.path.join(CSRC, "mask_cache.h")).read()
     probe = open(os.path.join(CSRC, "mask_probe.hip")).read()
-    assert '#include "mask_cache.h"' in sources["kernels.hip"] and '#include "mask_cache.h"' in sources["wave_common.h"]
+    assert '#include "mask_cache.h"' in sources["wave_common.h"]
     assert '#include "mask_cache.h"' in probe
     for name in PREDICATES + HELPERS:
         assert _defines(header, name), f"mask_cache.h does not define {name}"
@@ -66,6 +67,19 @@ def test_kernels_take_predicates_from_header():
     for f, text in sources.items():
         if any(re.search(r"\b" + re.escape(n.replace("struct ", "")) + r"\b", text) for n in PREDICATES + HELPERS):
             assert "mask_cache.h" in includes(f, set()), f"{f} uses the mask cache's code without its header"
+    # every unit that launches a cached row (MCACHE = true: `..., true>` in its sub-table of kernel_table.h) reaches the header
+    table = open(os.path.join(CSRC, "kernel_table.h")).read()
+    cached = {"MP_KERNELS_TILES": "kernels_tiles.hip", "MP_KERNELS_AOV": "kernels_aov.hip", "MP_KERNELS_PATHS": "kernels_paths.hip"}
+    for sub in re.findall(r"#define (MP_KERNELS_\w+)\(X\)", table):
+        rows = re.search(r"#define %s\(X\)((?:[^\n]*\\\n)*[^\n]*\n)" % sub, table).group(1)
+        # MCACHE is the fifth argument of the packet and feature-plane kernels and the fourth of the path kernel; nothing else has one
+        has_cached = re.search(r"\b(render_tiles_packet_kernel|render_aov_packet_kernel)<([^,>]+,){4} true>|\brender_paths_kernel<([^,>]+,){3} true>", rows)
+        assert (has_cached is not None) == (sub in cached), f"{sub}: the sub-tables with cached rows are {sorted(cached)}"
+    for sub, unit in cached.items():
+        assert "MP_FAMILY_LAUNCHER(%s)" % sub in sources[unit]
+        assert {"mask_cache.h", "packet_walk.h"} <= includes(unit, set()), f"{unit} launches cached rows without the mask cache's header"
     # the walk uses them
+    walk = [f for f, text in sources.items() if re.search(r"\bbool trace_packet_cached\(", text)]
+    assert walk == ["packet_walk.h"], walk
     for name in ["mask_cache_ray_ok(", "mask_cache_begin_pass(", "bounds_may_hit<OCT>(", "tri_may_hit(", "slab<"]:
-        assert name in sources["kernels.hip"], f"kernels.hip no longer calls {name}"
+        assert name in sources[walk[0]], f"{walk[0]} no longer calls {name}"

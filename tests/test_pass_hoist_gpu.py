@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of what the cached packet kernels do once per work unit instead of once per pass (kernels.hip): the sample key
+"""GPU tests (-m gpu) of what the cached packet kernels do once per work unit instead of once per pass (kernels_tiles.hip, kernels_aov.hip): the sample key
 from the lane's key at sample 0, the scene pre-test decided per unit (mask_cache.h, mask_cache_unit_reaches), and the shading normal's
 short normalisation (ray_math.h, unit_normal).  Frames against the oracle's bits, with the kernels named, at 96 x 64 in tiles of 32:
 64 samples on render_tiles_packet_kernel<16, ..., true> (four passes per unit, sixteen samples in flight) and 32 samples on

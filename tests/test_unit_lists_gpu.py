@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the cached packet walk's per-unit child lists (mask_cache.h unit_list_build; kernels.hip trace_packet_cached).
+"""GPU tests (-m gpu) of the cached packet walk's per-unit child lists (mask_cache.h unit_list_build; packet_walk.h trace_packet_cached).
 
 A. The list builder itself, through the probe (mask_probe.hip, mp_mask_probe_list: the function the walk calls, behind a real call
    as in the walk), dword for dword against the numpy model (tests/unit_list_model.py build_list): the returned table value, the
@@ -12,10 +12,12 @@ B. Frames, bit-equal to the oracle, with the kernels named: the teapot at 16 and
    eviction frame again in the `lists_tiny` build of the library (minipath_amd/csrc/Makefile: four table slots, 32 arena entries),
    which counts its evictions, arena resets and the passes it leaves to the uncached walk.  The floors are a quarter of the rates
    the model counts on 38 units of that frame (tests/test_unit_lists_cpu.py: 0.21 evictions, 0.53 resets and 0.53 such passes per
-   unit; the frame has 1 536 units of four passes).
+   unit; the frame has 1 536 units of four passes).  That build once more for the counters themselves: the fused tiles, the feature
+   planes and the fused paths are translation units with a copy of the counters each, and what the library reports is their sum.
 
 Run as a program (the variant's process: MINIPATH_HIP_SO is read when the package loads) this file renders that frame under both
-formats and writes the images and the counters to the .npz it is given."""
+formats and writes the images and the counters to the .npz it is given; with `counters` before the file name, one teapot frame
+from each of the three units and the counters after each."""
 import ctypes as C
 import os
 import subprocess
@@ -58,8 +60,45 @@ def render_variant(dst):
     np.savez(dst, **out)
 
 
+def count_families(dst):
+    """a counted build: one teapot frame from each unit that runs the cached walk (fused tiles, feature planes, fused paths), the
+    ten counters read -- summed over the units' copies -- after a reset and after every frame, then read with a reset and once more"""
+    import torch
+
+    import minipath_amd as mp
+    from minipath_amd import _lib
+    from tests.conftest import TEAPOT
+    from tests.unit_list_frames import frame, planes
+
+    lib = _lib.lib()
+    lib.mp_prof_read_n.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
+
+    def read(reset):
+        cnt = (C.c_ulonglong * 10)()
+        torch.cuda.synchronize()
+        assert lib.mp_prof_read_n(cnt, 10, reset) == 0
+        return [int(v) for v in cnt]
+
+    ctx = mp.Context(0)
+    obj = mp.TriangleBvh.with_obj(TEAPOT, ctx)
+    cam, res, seed, ts = mp.Camera.teapot_view(), (64, 48), 21, 32
+    read(1)
+    rows, names = [read(0)], []
+    names.append(frame(ctx, obj, cam, mp.RenderSettings(ts, 16, res, seed=seed))[2])
+    rows.append(read(0))
+    names.append(planes(ctx, obj, cam, mp.RenderSettings(ts, 16, res, seed=seed), ("ids", "albedo", "normal"))[1])
+    rows.append(read(0))
+    names.append(frame(ctx, obj, cam, mp.RenderSettings(ts, 32, res, seed=seed, max_depth=2))[2])
+    rows.append(read(0))
+    np.savez(dst, names=np.array(["\n".join(n) for n in names]), counters=np.array(rows, np.uint64), with_reset=np.array(read(1), np.uint64),
+             after_reset=np.array(read(0), np.uint64))
+
+
 if __name__ == "__main__":
-    render_variant(sys.argv[1])
+    if sys.argv[1] == "counters":
+        count_families(sys.argv[2])
+    else:
+        render_variant(sys.argv[1])
     sys.exit(0)
 
 import pytest  # noqa: E402
@@ -288,3 +327,29 @@ def test_atrium_frame_with_a_tiny_table_and_arena(oracle, tmp_path):
             assert diff == 0, (slots, diff)
             assert evictions >= units * 0.21 / 4 and resets >= units * 0.53 / 4 and left >= units * 0.53 / 4, (slots, evictions, resets, left)
             assert builds >= units and left <= resets
+
+
+def test_counters_are_summed_over_the_units_that_run_the_cached_walk(tmp_path):
+    """The fused tiles, the feature planes and the fused paths are translation units of their own, each with its own copy of the
+    counted build's counters; mp_prof_read_n reports their sum and resets them all.  The teapot at (64, 48), one frame per unit: the
+    packet kernel and the feature planes at 16 spp, and a depth-2 path frame at 32 spp -- the fewest samples at which the plan names
+    the path kernel's cached row (launch_plan.cpp; at 16 it names the row without a cache, which counts nothing).  Slot 0, list
+    builds, grows with every frame: no unit's counters are lost.  Exact counts are the business of the tests above."""
+    so = os.path.join(CSRC, "libminipath_hip_lists_tiny.so")
+    if not os.path.exists(so):
+        pytest.fail(f"{so} missing: run build() first")
+    dst = str(tmp_path / "counters.npz")
+    flags = ["-s"] if sys.flags.no_user_site else []
+    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), "counters", dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    with np.load(dst) as z:
+        names = [n.split("\n") for n in z["names"]]
+        counters, with_reset, after_reset = z["counters"], z["with_reset"], z["after_reset"]
+    print("list builds after the reset and after each frame:", counters[:, 0].tolist())
+    assert names == [["render_tiles_packet_kernel<4, false, 8, false, true>"], ["render_aov_packet_kernel<4, false, 8, false, true>"],
+                     ["render_paths_kernel<8, false, false, true>"]], names
+    assert counters.shape == (4, 10) and not counters[0].any(), "all ten counters are zero after a reset"
+    assert counters[0, 0] < counters[1, 0] < counters[2, 0] < counters[3, 0], counters[:, 0]
+    assert np.array_equal(with_reset, counters[3]), "a read with reset = 1 still reports what was counted"
+    assert not after_reset.any(), "... and leaves every unit's copy at zero"

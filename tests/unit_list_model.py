@@ -1,5 +1,5 @@
 """A numpy restatement of the cached packet walk's per-unit child LISTS (minipath_amd/csrc/mask_cache.h, unit_list_build, and
-kernels.hip, trace_packet_cached), on exported trees (TriangleBvh.device_tree: the packet tree, 16 slots, or the wide tree, 8).
+packet_walk.h, trace_packet_cached), on exported trees (TriangleBvh.device_tree: the packet tree, 16 slots, or the wide tree, 8).
 
 build_list     the list of one node under a unit's bounds B, entry for entry what unit_list_build appends to the arena
 list_unit_walk the walk of one unit over lists: node table (tag compare, direct-mapped on node_slot), arena, the reset when a list

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the cached packet walk (kernels.hip, trace_packet_cached) costs per pass on trees of several widths, counted on the CPU
+"""What the cached packet walk (packet_walk.h, trace_packet_cached) costs per pass on trees of several widths, counted on the CPU
 before any kernel work: the reference tree collapsed to at most LIMIT slots per node (sim_collapse.build_device, policy "area":
 the device trees' rule -- 8 = the wide tree, 16 = the packet tree), walked by a numpy model of the cached walk with the unit
 bounds of mask_cache_begin_unit (corner rays + 1/64; analytic_bounds.Cache), the per-unit node masks (box_reject) and triangle

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where the triangle tests of the cached packet walk end, and what two rules change, counted on the CPU: the library's exported
-packet tree walked by a numpy restatement of trace_packet_cached (kernels.hip) over child lists (tests/unit_list_model.py: build_list,
+packet tree walked by a numpy restatement of trace_packet_cached (packet_walk.h) over child lists (tests/unit_list_model.py: build_list,
 node_slot; its list_unit_walk is the check of this walk), the unit triangle masks by tools/sim_tri_reject.py's interval test, on the
 metric's frame (1920 x 1080, units of 2 x 2 pixels x 16 samples per pass, rays from the oracle, unit bounds from the corner rays at
 the shipped margin; unit-pick seed 11).
