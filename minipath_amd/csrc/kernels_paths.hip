@@ -2,6 +2,13 @@
 // per-wave pool in global memory.
 // One translation unit and one code object of libminipath_hip.so (kernel_table.h); the lane mapping and the arithmetic contract
 // are described in kernels.hip.
+// The unit triangle masks of this family stay without their far-side terms (mask_cache.h, tri_may_hit): only the camera pass of a
+// path runs the cached walk, the terms gain nothing measurable here (the stand-in's depth-8 paths: 546.2 against 546.8 ms), and
+// leaf_mask_slow's changed register use moved these kernels' allocation, which cost the teapot's depth-8 paths 2.7 % (45.47 ->
+// 46.71 ms over five alternating rounds, profiles/mask_far_notes.md).  Without them the unit's device code is what it was.
+#ifndef MP_NO_MASK_FAR
+#define MP_NO_MASK_FAR
+#endif
 #include "packet_walk.h"
 #include "render_state.h"
 #include "path_shading.h"

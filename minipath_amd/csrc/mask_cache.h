@@ -2,7 +2,7 @@
 // prove a child box or a triangle missed by every ray inside B, and the pass-entry checks that keep B valid.  A header of its own so
 // that a probe (mask_probe.hip, libmp_mask_probe.so) compiles the very functions the walk inlines and checks them against the
 // per-ray arithmetic of the reference at the corners of B (tests/test_mask_cache_gpu.py).  Device code only; the includer may define
-// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES / MP_ARENA_ENTRIES / MP_NODE_SLOT_MASK / MP_NO_FAR_EXIT before including it.
+// MP_PROF_COUNT (profiling builds) and MP_MCACHE_PAD / MP_MCACHE_MARGIN / MP_NODE_ENTRIES / MP_LEAF_ENTRIES / MP_ARENA_ENTRIES / MP_NODE_SLOT_MASK / MP_NO_FAR_EXIT / MP_NO_MASK_FAR before including it.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -504,6 +504,17 @@ __device__ __forceinline__ uint32_t unit_list_build(const float4* __restrict__ r
 // mask_cache_begin_pass), which keeps all intermediate bounds finite up to the reciprocal (|t numerator| < 2^98); a determinant
 // interval that touches zero or has an infinite reciprocal keeps the triangle; after that every value is one product of finite
 // numbers (never NaN), and the only sum (u + v) can at worst be inf - inf = NaN, which compares false and keeps the triangle.
+// The far side alone: u.lo > 1 or v.lo > 1 also skips the triangle.  `u.lo + v.lo > 1` does not cover it: where v.lo is negative
+// the sum can stay at or below 1 although every ray of the unit has u > 1, and each pass then loads the record only to leave at an
+// early-out.  u.lo bounds from below the very f32 u of every ray inside B (the corner argument above), so u.lo > 1 gives u > 1 for
+// all of them, and the walk accepts a ray only with !(min(u, v, t) < 0) & (u + v <= 1) (packet_walk.h, triangle.rs:125-129): with
+// u > 1, a negative v fails the first test; a NaN v fails it as triangle.rs writes it (v >= 0) and, where a minNum chain drops it,
+// makes u + v NaN, which fails the second; a v >= 0 (-0 included, u + -0 = u) gives fl(u + v) >= fl(u + 0) = u > 1, rounding being
+// monotone, and fails the second.  The same with u and v exchanged.  The comparisons are strict: a ray through v1
+// (u == 1, v == 0), through v2 (u == 0, v == 1) or on the far edge (u + v == 1) is accepted, and u.lo <= 1, v.lo <= 1 and
+// u.lo + v.lo <= 1 there keep the triangle.  A NaN bound compares false and keeps it.  Counted (tools/tri_exit_count.py,
+// profiles/mask_far_notes.md): the two terms take 11.6 surviving triangle tests per pass of the metric's frame to 9.6, none of the
+// dropped ones accepted by any ray of its unit.  -DMP_NO_MASK_FAR: the rule without them (A/B builds, tools/build_variant.sh).
 struct Iv {
     float lo, hi;
 };
@@ -524,8 +535,10 @@ __device__ __forceinline__ Iv iv_fma(const Iv a, const Iv b, const Iv z) {  // f
     const float h1 = __builtin_fmaf(a.lo, b.lo, z.hi), h2 = __builtin_fmaf(a.lo, b.hi, z.hi), h3 = __builtin_fmaf(a.hi, b.lo, z.hi), h4 = __builtin_fmaf(a.hi, b.hi, z.hi);
     return Iv{fminf(fminf(l1, l2), fminf(l3, l4)), fmaxf(fmaxf(h1, h2), fmaxf(h3, h4))};
 }
-// can any ray with origin / direction inside the bounds `b` (mask-cache header) hit the triangle {v0, e1, e2}?
-__device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3], const float (&e1)[3], const float (&e2)[3]) {
+// can any ray with origin / direction inside the bounds `b` (mask-cache header) hit the triangle {v0, e1, e2}?  far_only (the probe's;
+// the walk passes none and the stores fold away): set when the far-side terms alone say no
+__device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3], const float (&e1)[3], const float (&e2)[3], bool* far_only = nullptr) {
+    if (far_only) *far_only = false;
     const Iv d[3] = {Iv{b[13], b[16]}, Iv{b[14], b[17]}, Iv{b[15], b[18]}};
     // h = (fms(dy, e2z, dz * e2y), fms(dz, e2x, dx * e2z), fms(dx, e2y, dy * e2x)) ; fms(a, b, c) = fma(a, b, -c)
     const Iv h[3] = {iv_fma_c(d[1], e2[2], iv_neg(iv_mul_c(d[2], e2[1]))), iv_fma_c(d[2], e2[0], iv_neg(iv_mul_c(d[0], e2[2]))),
@@ -542,7 +555,13 @@ __device__ __forceinline__ bool tri_may_hit(const float* b, const float (&v0)[3]
     const Iv v = iv_mul(inv, iv_fma(d[2], q[2], iv_fma(d[1], q[1], iv_mul(d[0], q[0]))));
     const Iv t = iv_mul(inv, iv_fma_c(q[2], e2[2], iv_fma_c(q[1], e2[1], iv_mul_c(q[0], e2[0]))));
     const bool miss = u.hi < 0.0f || v.hi < 0.0f || (u.lo + v.lo) > 1.0f || t.hi < 0.0f;
-    return !miss;
+#ifndef MP_NO_MASK_FAR
+    const bool far = u.lo > 1.0f || v.lo > 1.0f;
+#else
+    const bool far = false;
+#endif
+    if (far_only) *far_only = far && !miss;
+    return !(miss || far);
 }
 
 // ---- the per-ray early-outs of a triangle test: "surely rejected" before the division ------------------------------------------------

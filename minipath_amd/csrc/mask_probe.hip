@@ -2,6 +2,7 @@
 // (tests/test_mask_cache_gpu.py), built with the library's flags.  Each entry point generates its cases on the device from a seed
 // and a counter-based hash and checks the predicate that the walk inlines against the walk's own per-ray arithmetic:
 //   * tri_may_hit against the per-ray Moeller-Trumbore sequence (triangle.rs:183-217, `1.0f / det`) of 192 rays inside B;
+//   * tri_may_hit once more on boxes beyond a triangle's far edges and on exact-boundary rays (tests/test_mask_far_side_gpu.py);
 //   * tri_exit1_key / tri_exit2_key (the walk's early-outs of a triangle test, as a wave decides them) against the same per-ray
 //     sequence of 64 rays inside B (tests/test_tri_exits_gpu.py);
 //   * bounds_may_hit<OCT> against slab<false, OCT> (aabb.rs:254-284, limit FLT_MAX) of 192 rays inside B, all eight patterns;
@@ -300,6 +301,132 @@ __global__ void exit_kernel(uint64_t seed, uint64_t base, uint64_t ncases, unsig
     const bool left = exit1 || exit2;
     record_case(out, left && any, c, any, exit1, exit2 && !exit1);
     if (lane == 0u && left && !(near1 || near2)) atomicAdd(out + 6, 1ull);
+}
+
+// ---- (a'') tri_may_hit beyond the far edges ----------------------------------------------------------------------------------------
+// Cases the generator above rarely gives: boxes whose rays all pass the triangle's plane beyond the edge u = 1 (or v = 1) while the
+// other coordinate's interval straddles zero, so that only the far-side terms of tri_may_hit (u.lo > 1, v.lo > 1) can reject; and
+// exact-boundary cases, where one corner ray of the box computes u == 1 & v == 0, u == 0 & v == 1 or u + v == 1 exactly, is
+// accepted, and the strict comparisons must keep the triangle.  Both are built in a local frame -- the triangle {p0, p0 + (sx, 0, 0),
+// p0 + (0, sy, 0)} (plus a small tilt in the first family), rays going down -z from a height H -- and then moved to world axes by a
+// permutation and sign flips of the axes (a mirror image has the same hits).
+//   far family (5 cases in 8): the footprint [a0, a1] x [b0, b1] of the box in (u, v), a0 > 1, b1 >= 0 and b0 around 1 - a0, comes
+//     from the origin bounds (directions nearly parallel) or from the direction bounds (origins nearly a point); u and v swapped
+//     in half the cases.
+//   exact family: every coordinate a small integer multiple of a power of two q, sx and sy powers of two, direction (+-0, +-0, -1):
+//     un, vn, det and the quotients are exact.  The aimed point is v1, v2, a dyadic point of the edge v1 v2, or such a point moved one
+//     ulp inside or outside; each coordinate of the box is that ray's value alone or extends from it to one side, upwards (away from
+//     the triangle in x and y) more often than not, so the ray is a corner of the box; one case in eight lets the direction
+//     bounds reach into the triangle's plane (the determinant interval touches zero), one in eight has a vertex at the cap 2^30.
+// Counters: [0] violations, [1] cases, [2] first violating case, [3] cases some ray hits, [4] cases rejected, [5] cases that only the
+// far-side terms reject, [6] cases kept in which a ray with u == 1, v == 1 or u + v == 1 exactly is accepted.
+__device__ __forceinline__ void gen_far_case(uint64_t seed, uint64_t c, float (&b)[20], float (&v0)[3], float (&v1)[3], float (&v2)[3]) {
+    float llo[6], lhi[6], p0[3], p1[3], p2[3];  // local frame: ray box (origin, direction) and vertices
+    const uint64_t hm = hsh(seed, c, 100);
+    if ((hm & 7u) < 5u) {
+        const float S = as_f((127u - 8u + static_cast<uint32_t>(hm >> 8) % 29u) << 23);
+        const float sx = S * (0.5f + unit(hsh(seed, c, 101))), sy = S * (0.5f + unit(hsh(seed, c, 102)));
+        const float tilt = (hm & 0x300000u) == 0u ? 0.0f : 0.05f * S;
+        for (int k = 0; k < 3; k++) p0[k] = 4.0f * S * (2.0f * unit(hsh(seed, c, 103 + k)) - 1.0f);
+        const float E1[3] = {sx, tilt * (2.0f * unit(hsh(seed, c, 106)) - 1.0f), tilt * (2.0f * unit(hsh(seed, c, 107)) - 1.0f)};
+        const float E2[3] = {tilt * (2.0f * unit(hsh(seed, c, 108)) - 1.0f), sy, tilt * (2.0f * unit(hsh(seed, c, 109)) - 1.0f)};
+        for (int k = 0; k < 3; k++) { p1[k] = p0[k] + E1[k]; p2[k] = p0[k] + E2[k]; }
+        // the footprint in (u, v)
+        const uint64_t hf = hsh(seed, c, 110);
+        float a0 = 1.0f + as_f((127u - static_cast<uint32_t>(hf & 15u)) << 23) * (0.25f + unit(hsh(seed, c, 111)));  // 1 + 2^-15 .. 1 + 1.25
+        float a1 = a0 + 2.0f * unit(hsh(seed, c, 112)) * unit(hsh(seed, c, 113));
+        float b0 = 1.0f - a0 - (2.0f * unit(hsh(seed, c, 114)) - 0.5f);  // around 1 - a0, mostly below
+        float b1 = fmaxf(b0, (hf & 0x30u) == 0u ? -0.25f * unit(hsh(seed, c, 115)) : 0.5f * unit(hsh(seed, c, 115)));
+        if (hf & 0x100u) { float x = a0; a0 = b0; b0 = x; x = a1; a1 = b1; b1 = x; }  // v beyond its far edge instead
+        const float H = S * as_f((127u + 2u + static_cast<uint32_t>(hf >> 12) % 5u) << 23);
+        const float am = 0.5f * (a0 + a1), bm = 0.5f * (b0 + b1);
+        const float wz = (hf & 0x10000u) ? 0.0f : H * 0x1p-6f * unit(hsh(seed, c, 116));
+        const float wd = (hf & 0x60000u) == 0u ? 0.0f : as_f((127u - 10u - static_cast<uint32_t>(hf >> 20) % 12u) << 23);
+        if (hf & 0x200u) {  // by the origin bounds
+            llo[0] = p0[0] + a0 * sx; lhi[0] = p0[0] + a1 * sx;
+            llo[1] = p0[1] + b0 * sy; lhi[1] = p0[1] + b1 * sy;
+            llo[3] = -wd; lhi[3] = wd; llo[4] = -wd; lhi[4] = wd;
+        } else {  // by the direction bounds
+            const float wo = (hf & 0x400u) ? 0.0f : S * 0x1p-8f * unit(hsh(seed, c, 117));
+            llo[0] = p0[0] + am * sx - wo; lhi[0] = p0[0] + am * sx + wo;
+            llo[1] = p0[1] + bm * sy - wo; lhi[1] = p0[1] + bm * sy + wo;
+            llo[3] = (a0 - am) * sx / H; lhi[3] = (a1 - am) * sx / H;
+            llo[4] = (b0 - bm) * sy / H; lhi[4] = (b1 - bm) * sy / H;
+        }
+        llo[2] = p0[2] + H; lhi[2] = p0[2] + H + wz;
+        llo[5] = -1.0f; lhi[5] = -1.0f + wd;
+    } else {
+        const bool cap = ((hm >> 8) & 7u) == 0u, plane = ((hm >> 11) & 7u) == 0u;
+        const float q = cap ? 0x1p20f : as_f((127u - 20u + static_cast<uint32_t>(hm >> 16) % 36u) << 23);
+        const float sx = q * as_f((127u + 4u + static_cast<uint32_t>(hm >> 24) % 5u) << 23), sy = q * as_f((127u + 4u + static_cast<uint32_t>(hm >> 28) % 5u) << 23);
+        for (int k = 0; k < 3; k++) p0[k] = q * (static_cast<float>(static_cast<uint32_t>(hsh(seed, c, 120 + k) >> 40) % 1025u) - 512.0f);
+        if (cap) { p0[0] = 0x1p30f - sx; p0[1] = -0x1p30f; }  // v1.x at the cap, v0.y and v1.y at its negative
+        for (int k = 0; k < 3; k++) { p1[k] = p0[k]; p2[k] = p0[k]; }
+        p1[0] = p0[0] + sx; p2[1] = p0[1] + sy;
+        // the aimed point (a, 1 - a) of the edge v1 v2: a = 1 (v1), 0 (v2) or k / 16
+        const uint64_t hp = hsh(seed, c, 123);
+        const uint32_t place = static_cast<uint32_t>(hp & 7u);  // 0, 1: v1; 2, 3: v2; 4: on the edge; 5: inside by an ulp; 6: outside by an ulp; 7: on the edge
+        const float a = place < 2u ? 1.0f : place < 4u ? 0.0f : static_cast<float>(1u + static_cast<uint32_t>(hp >> 8) % 15u) * 0.0625f;
+        float x[6] = {p0[0] + a * sx, p0[1] + (1.0f - a) * sy, p0[2] + q * static_cast<float>(1u + static_cast<uint32_t>(hp >> 16) % 4096u),
+                      (hp & 0x10000000u) ? -0.0f : 0.0f, (hp & 0x20000000u) ? -0.0f : 0.0f, -1.0f};
+        const bool along_x = (hp >> 30) & 1u;  // the coordinate the hair moves: towards the triangle is down in x and in y
+        if (place == 5u) x[along_x ? 0 : 1] = step(x[along_x ? 0 : 1], false);
+        if (place == 6u) x[along_x ? 0 : 1] = step(x[along_x ? 0 : 1], true);
+        for (int k = 0; k < 6; k++) {
+            const uint64_t hk = hsh(seed, c, 130 + k);
+            const uint32_t side = static_cast<uint32_t>(hk & 7u);  // 0..2: the value alone; 3..5: upwards; 6, 7: downwards
+            const float w = k < 3 ? q * as_f((127u - 2u + static_cast<uint32_t>(hk >> 8) % 12u) << 23) : as_f((127u - 20u + static_cast<uint32_t>(hk >> 8) % 18u) << 23);
+            llo[k] = side >= 6u ? x[k] - w : x[k];
+            lhi[k] = (side >= 3u && side < 6u) ? x[k] + w : x[k];
+        }
+        if (plane) { llo[5] = -1.0f; lhi[5] = 0.0f; }
+    }
+    // to world axes: world[k] = sg[k] * local[pm[k]]
+    const uint64_t hw = hsh(seed, c, 140);
+    const uint32_t rot = static_cast<uint32_t>(hw & 0xFFu) % 6u;
+    const int pm[3] = {static_cast<int>(rot % 3u), static_cast<int>((rot % 3u + 1u + rot / 3u) % 3u), static_cast<int>((rot % 3u + 2u - rot / 3u) % 3u)};
+    float lo[6], hi[6];
+    for (int k = 0; k < 3; k++) {
+        const float sg = ((hw >> (8 + k)) & 1u) ? -1.0f : 1.0f;
+        v0[k] = sg * p0[pm[k]]; v1[k] = sg * p1[pm[k]]; v2[k] = sg * p2[pm[k]];
+        for (int g = 0; g < 2; g++) {
+            const float e0 = sg * llo[3 * g + pm[k]], e1 = sg * lhi[3 * g + pm[k]];
+            lo[3 * g + k] = sg < 0.0f ? e1 : e0;
+            hi[3 * g + k] = sg < 0.0f ? e0 : e1;
+        }
+    }
+    clamp_vertex(v0); clamp_vertex(v1); clamp_vertex(v2);
+    for (int k = 0; k < 3; k++) {
+        b[k] = clampf(lo[k], -kOrgCap, kOrgCap); b[3 + k] = clampf(hi[k], -kOrgCap, kOrgCap);
+        b[13 + k] = clampf(lo[3 + k], -2.0f, 2.0f); b[16 + k] = clampf(hi[3 + k], -2.0f, 2.0f);
+    }
+    for (int i = 6; i < 13; i++) b[i] = 0.0f;
+    b[19] = 0.0f;
+}
+
+__global__ void far_kernel(uint64_t seed, uint64_t base, uint64_t ncases, unsigned long long* out, uint32_t*) {
+    const uint64_t c = base + (static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x) / 64u;
+    const uint32_t lane = threadIdx.x & 63u;
+    if (c >= ncases) return;  // (whole waves)
+    float b[20], v0[3], v1[3], v2[3];
+    gen_far_case(seed, c, b, v0, v1, v2);
+    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]}, e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    float lo[6], hi[6];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { lo[k] = b[k]; hi[k] = b[3 + k]; lo[3 + k] = b[13 + k]; hi[3 + k] = b[16 + k]; }
+    bool far_only = false;
+    const bool keep = tri_may_hit(b, v0, e1, e2, &far_only);
+    bool hit = false, on_edge = false;
+    for (uint32_t s = 0; s < 3; s++) {
+        float x[6];
+        case_ray(lo, hi, s * 64u + lane, seed, c, x);
+        const TriRay tr = mt_ray(x, v0, e1, e2);
+        hit |= tr.hit;
+        on_edge |= tr.hit && (tr.u == 1.0f || tr.v == 1.0f || (tr.u + tr.v) == 1.0f);
+    }
+    const bool any = __ballot(hit) != 0, any_edge = __ballot(on_edge) != 0;
+    record_case(out, !keep && any, c, any, !keep, far_only);
+    if (lane == 0u && keep && any_edge) atomicAdd(out + 6, 1ull);
 }
 
 // ---- (b) bounds_may_hit<OCT> -------------------------------------------------------------------------------------------------------
@@ -764,6 +891,8 @@ extern "C" {
 int mp_mask_probe_tri(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(tri_kernel, seed, ncases, nullptr, out); }
 // (a') tri_exit1_key / tri_exit2_key, the wave's decision: ncases cases
 int mp_mask_probe_exits(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(exit_kernel, seed, ncases, nullptr, out); }
+// (a'') tri_may_hit on boxes beyond the far edges and on exact-boundary cases: ncases cases
+int mp_mask_probe_far(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(far_kernel, seed, ncases, nullptr, out); }
 // (b) bounds_may_hit<OCT>: ncases cases, case c of pattern c & 7
 int mp_mask_probe_box(uint64_t seed, uint64_t ncases, unsigned long long* out) { return run_cases(box_kernel, seed, ncases, nullptr, out); }
 // (a) / (b) with a dump of every case to `host` (ncases * mp_mask_probe_dump_dwords() dwords): kind 0 triangles, 1 boxes

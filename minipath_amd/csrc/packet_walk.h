@@ -130,6 +130,11 @@ __device__ __noinline__ uint64_t leaf_mask_slow(const float* __restrict__ tris_a
         keep = tri_may_hit(reinterpret_cast<const float*>(mcache), v0, e1, e2);
     }
     const uint64_t todo = __ballot(keep);
+#if defined(MP_PROF_MISSES) && defined(MP_PROF_MASK_TRIS)
+    // counted builds with -DMP_PROF_MASK_TRIS: slot 2 is the number of triangles the built masks keep (not the inner links followed),
+    // so slot 2 / slot 1 is the mean popcount of a stored mask (tools/cache_miss_count.py, tests/test_mask_far_side_gpu.py)
+    if (j == 0u) atomicAdd(&g_prof[2], static_cast<unsigned long long>(__popcll(todo)));
+#endif
     if (j == 0u) {
         const uint32_t ls = first & static_cast<uint32_t>(kLeafCacheEntries - 1);
         mcache[kLeafTagBase + ls] = first;
@@ -386,7 +391,9 @@ __device__ __forceinline__ bool trace_packet_cached(const DevScene& sc, const Ra
         const uint32_t link = uniform_u(rec[6]);
         float lim = ok ? best_t : -1.0f;  // best.t for the rays this child is live for, -1 for the others: no slab interval and no hit distance passes
         if ((link & 63u) == 0u) {  // inner node (device link, mp_internal.h)
+#ifndef MP_PROF_MASK_TRIS  // (that build counts surviving triangles in this slot: leaf_mask_slow)
             MP_PROF_COUNT(2);
+#endif
             const uint32_t node = link >> 6;
             const uint32_t slot = node_slot(node);
             const uint32_t tag = __builtin_amdgcn_readfirstlane(mcache[static_cast<uint32_t>(kMaskCacheHeader) + slot]);

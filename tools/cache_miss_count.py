@@ -30,3 +30,7 @@ print(f"{which} x{spp}: per unit: node-list slow paths {out[0] / units:.1f}, lea
       f" per pass: node visits (inner links followed) {out[2] / passes:.2f}")
 print(f"{which} x{spp}: per unit: node-table evictions {out[4] / units:.3f}, arena resets {out[5] / units:.4f}; passes left to the uncached walk: {out[6]} of {passes}")
 print(f"{which} x{spp}: per pass: pops skipped on an empty-mask leaf {out[7] / passes:.3f}")
+if len(sys.argv) > 3 and sys.argv[3] == "mask-tris":
+    # a build with -DMP_PROF_MASK_TRIS as well: slot 2 is not the inner links followed (the "node visits" above) but the triangles
+    # the built leaf masks keep, so slot 2 / slot 1 is the mean popcount of a stored mask (the model: tools/tri_exit_count.py)
+    print(f"{which} x{spp}: per leaf-mask build: surviving triangles {out[2] / max(out[1], 1):.2f} ({out[2]} in {out[1]} builds); the node visits above are not counted in this build")

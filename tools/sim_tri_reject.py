@@ -73,8 +73,10 @@ def fms(a, b, c):
     return fma(a, b, neg(c))
 
 
-def interval_reject(v0, e1, e2, olo, ohi, dlo, dhi):
-    """[m] bool: no ray with origin / direction inside the boxes can pass u >= 0, v >= 0, u + v <= 1, t >= 0"""
+def interval_reject(v0, e1, e2, olo, ohi, dlo, dhi, far=True):
+    """[m] bool: no ray with origin / direction inside the boxes can pass u >= 0, v >= 0, u + v <= 1, t >= 0.  far: the shipped rule
+    (mask_cache.h, tri_may_hit), which also rejects when u > 1 or v > 1 for every ray; far=False is the rule before it (what
+    -DMP_NO_MASK_FAR builds), kept so that both can be counted."""
     m = v0.shape[0]
     P = lambda x: Iv(x, x)
     d = [Iv(np.full(m, dlo[k], F), np.full(m, dhi[k], F)) for k in range(3)]
@@ -91,6 +93,8 @@ def interval_reject(v0, e1, e2, olo, ohi, dlo, dhi):
         v = mul(inv, dot(d, q))
         t = mul(inv, dot(E2, q))
         rej = (u.hi < 0) | (v.hi < 0) | ((u.lo + v.lo) > 1) | (t.hi < 0)
+        if far:
+            rej |= (u.lo > 1) | (v.lo > 1)
     return rej & ~straddle & np.isfinite(inv.lo) & np.isfinite(inv.hi)
 
 

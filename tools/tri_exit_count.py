@@ -9,6 +9,9 @@ Rule 1 (mask_cache.h, tri_exit1_key / tri_exit2_key): a wave leaves a triangle b
 rejected -- today on the near side (a numerator surely negative), now also on the far side (u, or u + v, surely above 1).
 Rule 2 (trace_packet_cached): a list entry whose leaf has an empty unit triangle mask is marked by the visit that finds it so; later
 pops of the entry stop at the mark.
+Rule 3 (mask_cache.h, tri_may_hit): the unit triangle mask also drops a triangle when u > 1 or v > 1 for every ray inside the unit's
+bounds (sim_tri_reject.interval_reject, far=True).  Every unit is walked under the masks without and with it: surviving tests, where
+the removed tests would have ended, empty-mask leaf pops and pops stopped at a mark under each.
 
 Asserted on every counted pass: no triangle that either form of rule 1 leaves is accepted by a live ray; no triangle the unit mask
 drops is accepted by a live ray; every ray's best.t is bit-equal with and without the skip, and equal to the model's list walk.
@@ -51,8 +54,9 @@ def main():
     nodes, root = host.device_tree(packet=True)[:2]
     root_rec = nodes.shape[0] * nodes.shape[1]
     keys = ("pops", "leaf_pops", "leaf_culled", "leaf_visits", "empty_pops", "empty_visits", "skipped", "tests", "old1", "old2", "old_full",
-            "old_full_none", "new1", "new2", "new_full", "new_full_none", "some", "far_slack_lost")
-    cnt = {k: 0 for k in keys}
+            "old_full_none", "new1", "new2", "new_full", "new_full_none", "some", "far_slack_lost", "removed1", "removed2", "removed_full")
+    # one set of counts per rule of the unit triangle masks: False = without the far-side terms (-DMP_NO_MASK_FAR), True = the shipped rule
+    cnts = {far: {k: 0 for k in keys} for far in (False, True)}
 
     def dot(a, b):
         return fma32(a[2], b[2], fma32(a[1], b[1], F(a[0]) * F(b[0])))
@@ -65,14 +69,15 @@ def main():
             ok = np.abs(det) <= HUGE
         return np.where(ok, (num.view(np.uint32) ^ (det.view(np.uint32) & np.uint32(0x80000000))).view(F), F(1)).astype(F)
 
-    def leaf_visit(link, header, o, d, live, best, count):
-        """the leaf's surviving triangles for the live rays: the closest accepted t per ray (inf: none)"""
+    def leaf_visit(link, header, o, d, live, best, cnt, far):
+        """the leaf's surviving triangles for the live rays: the closest accepted t per ray (inf: none); cnt: the counts to add to, or None"""
         if link not in tris.cache:
             tris.nearest(link, o[:1], d[:1])
         v0, e1, e2 = tris.cache[link]
         lo, hi, _ = header
         with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-            keep = ~interval_reject(v0, e1, e2, lo[0], hi[0], lo[2], hi[2])
+            keep = ~interval_reject(v0, e1, e2, lo[0], hi[0], lo[2], hi[2], far=far)
+            removed = ~interval_reject(v0, e1, e2, lo[0], hi[0], lo[2], hi[2], far=False) & ~keep  # what the far-side terms take out
             dd, oo = [d[:, None, k] for k in range(3)], [o[:, None, k] for k in range(3)]
             E1, E2, V0 = ([a[None, :, k] for k in range(3)] for a in (e1, e2, v0))
             h = [fms(dd[1], E2[2], dd[2] * E2[1]), fms(dd[2], E2[0], dd[0] * E2[2]), fms(dd[0], E2[1], dd[1] * E2[0])]
@@ -99,8 +104,11 @@ def main():
         assert not (some & ~keep).any(), "a triangle the unit mask drops is accepted by a live ray"
         assert not (some & (old1 | old2 | new1 | new2 | rule2)).any(), "a triangle the wave leaves is accepted by a live ray"
         assert not (old1 & ~new1).any() and not (old2 & ~new2).any()
-        if count:
+        if cnt is not None:
             k = keep
+            # where a removed triangle's test ends when it is still made (the walk with both early-outs): what its removal saves
+            cnt["removed1"] += int((removed & new1).sum()); cnt["removed2"] += int((removed & ~new1 & new2).sum())
+            cnt["removed_full"] += int((removed & ~new1 & ~new2).sum())
             cnt["tests"] += int(k.sum())
             cnt["old1"] += int((k & old1).sum()); cnt["old2"] += int((k & ~old1 & old2).sum())
             cnt["old_full"] += int((k & ~old1 & ~old2).sum()); cnt["old_full_none"] += int((k & ~old1 & ~old2 & ~some).sum())
@@ -111,7 +119,7 @@ def main():
         tt = np.where(acc & keep[None, :], t, F(np.inf))
         return tt.min(1).astype(F) if tt.shape[1] else np.full(o.shape[0], np.inf, F), bool(keep.any())
 
-    def walk_unit(header, rays, skip, count):
+    def walk_unit(header, rays, skip, cnt, far):
         """trace_packet_cached over one unit (ul.list_unit_walk with the leaf model above and rule 2): best t [passes, rays], or None
         for a unit with a pass that is left to the uncached walk (not what this tool counts)"""
         table, arena, marked, out, n = {}, [], set(), [], {"pops": 0, "skipped": 0}
@@ -136,17 +144,17 @@ def main():
                 ok = gm._slab(box, o, inv, np.where(cur[2], best, F(-1)))
                 if link & 63:
                     empty = None
-                    if count:
+                    if cnt is not None:
                         cnt["leaf_pops"] += 1
                     if not ok.any():
-                        if count:
+                        if cnt is not None:
                             cnt["leaf_culled"] += 1
                             # (is its mask empty?  only counted: the walk does not look)
-                            empty = not leaf_visit(link, header, o, d, ok, best, False)[1]
+                            empty = not leaf_visit(link, header, o, d, ok, best, None, far)[1]
                             cnt["empty_pops"] += empty
                         continue
-                    t, any_kept = leaf_visit(link, header, o, d, ok, best, count)
-                    if count:
+                    t, any_kept = leaf_visit(link, header, o, d, ok, best, cnt, far)
+                    if cnt is not None:
                         cnt["leaf_visits"] += 1
                         cnt["empty_pops"] += not any_kept
                         cnt["empty_visits"] += not any_kept
@@ -181,7 +189,7 @@ def main():
             self.header = header
 
         def nearest(self, link, o, d):
-            return leaf_visit(link, self.header, o, d, np.ones(o.shape[0], bool), None, False)[0]
+            return leaf_visit(link, self.header, o, d, np.ones(o.shape[0], bool), None, None, True)[0]
 
     rng = np.random.default_rng(11)
     n_units = n_pass = declined = 0
@@ -192,23 +200,31 @@ def main():
             declined += 1
             continue
         header, rays = up
-        saved = dict(cnt)
-        plain, n_plain = walk_unit(header, rays, False, True)
-        if plain is None:
-            cnt.update(saved)
+        saved = {far: dict(c) for far, c in cnts.items()}
+        walks = {far: walk_unit(header, rays, False, cnts[far], far) for far in (False, True)}
+        if walks[True][0] is None:  # (the lists do not depend on the triangle masks: both rules or neither)
+            assert walks[False][0] is None
+            for far in cnts:
+                cnts[far].update(saved[far])
             declined += 1
             continue
-        skipped, n_skip = walk_unit(header, rays, True, False)
-        assert n_plain["pops"] == n_skip["pops"] and n_plain["skipped"] == 0, "a pop that stops at a mark is still a pop of the list"
-        cnt["pops"] += n_plain["pops"]
-        cnt["skipped"] += n_skip["skipped"]
-        assert np.array_equal(plain.view(np.uint32), skipped.view(np.uint32)), "best.t differs with the skip"
+        plain = walks[True][0]
+        assert np.array_equal(plain.view(np.uint32), walks[False][0].view(np.uint32)), "best.t differs between the mask rules"
+        for far in (False, True):
+            skipped, n_skip = walk_unit(header, rays, True, None, far)
+            n_plain = walks[far][1]
+            assert n_plain["pops"] == n_skip["pops"] and n_plain["skipped"] == 0, "a pop that stops at a mark is still a pop of the list"
+            cnts[far]["pops"] += n_plain["pops"]
+            cnts[far]["skipped"] += n_skip["skipped"]
+            assert np.array_equal(plain.view(np.uint32), skipped.view(np.uint32)), "best.t differs with the skip"
         model, _, _ = ul.list_unit_walk(nodes, root, MaskedTriangles(header), header, rays, entries, arena_entries)
         assert np.array_equal(plain.view(np.uint32), model.view(np.uint32)), "best.t differs from the model's list walk"
         n_units += 1
         n_pass += len(rays)
 
+    cnt = cnts[True]
     p = lambda k: cnt[k] / n_pass
+    q = lambda k: cnts[False][k] / n_pass
     print(f"{scene}: {n_units} units x {passes} passes of 2x2 pixels x 16 samples ({declined} units skipped); packet tree, node table {entries}, arena {arena_entries}")
     print("asserted on every pass: no triangle a wave leaves early (either rule) or the unit mask drops is accepted by a live ray; best.t bit-equal with and")
     print("without the skip of marked entries, and equal to tests/unit_list_model.py's list walk")
@@ -218,6 +234,11 @@ def main():
     print(f"  leaf pops whose unit triangle mask is empty (visited) {p('empty_pops'):6.2f} ({p('empty_visits'):.2f})")
     print(f"  ... that stop at a mark (rule 2)                     {p('skipped'):7.2f}   pops that go on to the record load: {p('pops'):.2f} -> {p('pops') - p('skipped'):.2f}")
     print(f"  triangle tests (survivors of the unit masks)         {p('tests'):7.2f}")
+    print("  the unit masks without / with their far-side terms (u.lo > 1, v.lo > 1; every other line is with them):")
+    print(f"    triangle tests (survivors)                         {q('tests'):7.2f} -> {p('tests'):.2f}")
+    print(f"    the tests removed: would leave at the first early-out / at the second / run the division  {p('removed1'):.2f} / {p('removed2'):.2f} / {p('removed_full'):.2f}")
+    print(f"    leaf pops whose mask is empty (visited)            {q('empty_pops'):7.2f} ({q('empty_visits'):.2f}) -> {p('empty_pops'):.2f} ({p('empty_visits'):.2f})")
+    print(f"    pops that stop at a mark                           {q('skipped'):7.2f} -> {p('skipped'):.2f}")
     print(f"  {'':52s} {'near side only':>15s} {'with the far side':>18s}")
     for label, a, b in (("leave at the first early-out", "old1", "new1"), ("leave at the second", "old2", "new2"), ("run the division and the acceptance", "old_full", "new_full"),
                         ("... of those, accepted by no ray", "old_full_none", "new_full_none")):
