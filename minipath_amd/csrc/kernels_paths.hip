@@ -9,6 +9,11 @@
 #ifndef MP_NO_MASK_FAR
 #define MP_NO_MASK_FAR
 #endif
+// Nor does this family take the one-test pass entry (packet_walk.h, trace_packet): one pass in depth + 1 of a path is a camera pass,
+// so the saving is out of reach of a measurement here, while any change of these kernels' register allocation is not (above).
+#ifndef MP_NO_ENTRY_FOLD
+#define MP_NO_ENTRY_FOLD
+#endif
 #include "packet_walk.h"
 #include "render_state.h"
 #include "path_shading.h"

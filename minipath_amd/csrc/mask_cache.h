@@ -253,6 +253,46 @@ __device__ __forceinline__ void mask_cache_begin_pass(const MaskCache& mc, const
         wave_lds_sync();
     }
 }
+// ---- pass entry in one test: is the whole pass inside a valid B? ------------------------------------------------------------------
+// Called by every lane before anything else of a pass (packet_walk.h, trace_packet).  Returns B's sign pattern (0..7) when the
+// header holds a valid B (state = pattern | 0x100; no other bit, so not 0xFFFFFFFF) and no active lane's ray deviates from B in any of
+// its nine components; kNoPattern otherwise, and the pass takes the full route: mask_cache_ray_ok, the sign ballots,
+// mask_cache_begin_pass.  With a pattern the caller enters the cached walk of that pattern directly.  What the skipped guards would
+// have established follows from "inside a valid B":
+//   * Sign and finiteness.  A valid B was written by mask_cache_begin_unit or mask_cache_begin_pass from rays that had passed
+//     mask_cache_ray_ok and shared one sign pattern, and the widening of both keeps each inverse-direction bound finite, non-zero
+//     and of that sign (a widened bound that crosses or reaches zero, or overflows, is replaced by the unwidened one).  A component
+//     with lo <= v <= hi between two finite non-zero numbers of one sign is finite, non-zero and of that sign: no infinite inverse
+//     (the literal walk is not needed), every sign ballot uniform and equal to the header's pattern.
+//   * tri_may_hit's and bounds_may_hit's no-overflow bounds are bounds on B, not on the rays: B's direction bounds stay within 2 and
+//     its origin bounds within 2^31 (the caps of the same two widenings), whichever route the pass took.
+//   * A ray with an origin component between 2^30 and 2^31 in magnitude that lies inside B fails mask_cache_ray_ok and took a
+//     generic walk; here it takes the cached one.  The hits are the same: every walk computes the reference's, and the cached walk's
+//     exactness argument asks for rays inside B, nothing about 2^30.
+//   * NaN and infinity.  A deviation |v - med3(v, lo, hi)| is NaN for a NaN v and +inf for an infinite v (lo and hi are finite).  The
+//     nine are folded by ADDITION, not by maxNum as in mask_cache_begin_pass: maxNum drops a NaN operand, a sum keeps it, and a sum of
+//     non-negative terms is zero only if every term is (an overflow gives +inf).  The test is !(sum == 0), true for NaN: such a ray
+//     never enters here.  No separate NaN guard.
+// Inactive lanes may hold anything; their verdict is masked.  The decision steers work only.
+constexpr uint32_t kNoPattern = 8u;
+__device__ __forceinline__ uint32_t mask_cache_pass_inside(const MaskCache& mc, const Ray& r, bool active) {
+    float h[20];
+#pragma unroll
+    for (int i = 0; i < 5; i++) {
+        const float4 q = reinterpret_cast<const float4*>(mc.lds)[i];
+        h[4 * i] = q.x; h[4 * i + 1] = q.y; h[4 * i + 2] = q.z; h[4 * i + 3] = q.w;
+    }
+    const uint32_t state = __builtin_amdgcn_readfirstlane(as_u(h[kHdrState]));
+    const float val[3][3] = {{r.ox, r.oy, r.oz}, {r.ix, r.iy, r.iz}, {r.dx, r.dy, r.dz}};
+    float dev = 0.0f;
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) dev += bounds_deviation(val[g][k], h[hdr_lo(g) + k], h[hdr_lo(g) + 3 + k]);
+    }
+    const bool inside = __ballot(active && !(dev == 0.0f)) == 0;
+    return ((state & ~7u) == 0x100u && inside) ? (state & 7u) : kNoPattern;
+}
 // ---- B from the camera: the unit's bounds before its first pass ------------------------------------------------------------------
 // A unit's rays are a closed-form function of the camera (camera_rays.h): film points inside its pixel block (widened by the jitter) and lens points
 // inside the lens disc.  Origins and unnormalised directions are linear in (film_u, film_v, lens a, lens b), so over the box

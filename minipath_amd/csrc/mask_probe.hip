@@ -9,7 +9,8 @@
 //   * mask_cache_ray_ok against its plain definition, every f32 bit pattern in each of the nine components;
 //   * bounds_deviation against `v < lo || v > hi`;
 //   * mask_cache_begin_pass against a serial restatement of its rule, over sequences of passes per wave;
-//   * mask_cache_begin_unit's header for given cameras and pixel blocks, handed back for the host model of the test.
+//   * mask_cache_begin_unit's header for given cameras and pixel blocks, handed back for the host model of the test;
+//   * mask_cache_pass_inside's decision on passes the test makes by hand, handed back likewise (tests/test_pass_entry_gpu.py).
 // The 192 rays of a case are the 64 corners of its 6-D box (origin x direction or origin x inverse direction), those corners moved
 // one ulp inward in every coordinate, and 64 interior points (one in four snapped onto a face); one wave per case, lane l owns rays
 // l, 64 + l and 128 + l.  Counters (unsigned long long out[8]): [0] violations, [1] cases, [2] smallest violating case index (~0 if
@@ -836,6 +837,25 @@ __global__ void __launch_bounds__(256) list_kernel(const float4* recs, uint32_t 
     for (uint32_t i = lane; i < static_cast<uint32_t>(kArenaRoom); i += 64u) o[4u + i] = base[static_cast<uint32_t>(kArenaBase) + i];
 }
 
+// ---- (g) mask_cache_pass_inside: the pass-entry decision --------------------------------------------------------------------------
+// One wave per hand-made pass: the header (32 dwords) goes to the wave's cache as given, lane l's ray is rays[(case * 9 + i) * 64 + l]
+// (i = 0..2 origin, 3..5 inverse direction, 6..8 direction), bit l of active[case] says whether the lane is active.
+// out[case] = the returned pattern (0..7) or kNoPattern.
+__global__ void __launch_bounds__(256) entry_kernel(const uint32_t* headers, const float* rays, const uint64_t* active, uint32_t n, uint32_t* out) {
+    __shared__ __align__(16) uint32_t lds[4 * kMaskCacheHeader];
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t c = blockIdx.x * 4u + w;
+    if (c >= n) return;  // (whole waves)
+    uint32_t* const base = lds + w * kMaskCacheHeader;
+    if (lane < static_cast<uint32_t>(kMaskCacheHeader)) base[lane] = headers[static_cast<size_t>(c) * kMaskCacheHeader + lane];
+    wave_lds_sync();
+    const float* x = rays + static_cast<size_t>(c) * 9u * 64u + lane;
+    Ray r;
+    r.ox = x[0]; r.oy = x[64]; r.oz = x[128]; r.ix = x[192]; r.iy = x[256]; r.iz = x[320]; r.dx = x[384]; r.dy = x[448]; r.dz = x[512];
+    const uint32_t got = mask_cache_pass_inside(MaskCache{base}, r, ((active[c] >> lane) & 1ull) != 0ull);
+    if (lane == 0u) out[c] = got;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
 // One launch on a fresh counter buffer.  HIP's last-error state is per thread and sticky: an error that earlier work of the process
 // left there is not this probe's, so it is cleared before the launch, and every call's own status is checked (probe.hip).
@@ -988,6 +1008,32 @@ int mp_mask_probe_pass(uint64_t seed, uint64_t nwaves, unsigned long long* out) 
     return run([&](unsigned long long* d) {
         hipLaunchKernelGGL(pass_kernel, dim3(static_cast<uint32_t>(nwaves / 4)), dim3(256), 0, 0, seed, d);
     }, out);
+}
+// (g) mask_cache_pass_inside: ncases passes (host arrays: 32 header dwords, 9 x 64 ray components and one active mask per case) ->
+// one dword per case, the pattern or *no_pattern
+int mp_mask_probe_entry(const uint32_t* headers, const float* rays, const uint64_t* active, uint32_t ncases, uint32_t* out, uint32_t* no_pattern) {
+    (void)hipGetLastError();
+    *no_pattern = kNoPattern;
+    if (ncases == 0u) return 0;
+    uint32_t *dhdr = nullptr, *dout = nullptr;
+    float* drays = nullptr;
+    uint64_t* dact = nullptr;
+    const size_t hdr_bytes = sizeof(uint32_t) * kMaskCacheHeader * ncases, ray_bytes = sizeof(float) * 9u * 64u * ncases;
+    hipError_t e = hipMalloc(&dhdr, hdr_bytes);
+    if (e == hipSuccess) e = hipMalloc(&drays, ray_bytes);
+    if (e == hipSuccess) e = hipMalloc(&dact, sizeof(uint64_t) * ncases);
+    if (e == hipSuccess) e = hipMalloc(&dout, sizeof(uint32_t) * ncases);
+    if (e == hipSuccess) e = hipMemcpy(dhdr, headers, hdr_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(drays, rays, ray_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dact, active, sizeof(uint64_t) * ncases, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(entry_kernel, dim3((ncases + 3u) / 4u), dim3(256), 0, 0, dhdr, drays, dact, ncases, dout);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipDeviceSynchronize();
+        if (e == hipSuccess) e = hipMemcpy(out, dout, sizeof(uint32_t) * ncases, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(dhdr); (void)hipFree(drays); (void)hipFree(dact); (void)hipFree(dout);
+    return static_cast<int>(e);
 }
 // (f) unit_list_build: the tree `recs` (n_nodes nodes of `slots` records of 8 dwords, as mp_scene_device_tree exports it; every inner
 // link must name a node of it), ncases headers of 32 dwords and cases {node, arena entries in use} -> mp_mask_probe_list_dwords()

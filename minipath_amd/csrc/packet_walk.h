@@ -513,50 +513,84 @@ __device__ __forceinline__ void trace_packet(const DevScene& sc, const Ray& r, b
         // Kernels with a mask cache: the sign-specialised walks use it, and a pass with a ray that fails mask_cache_ray_ok takes a
         // generic walk.  The same choices as below, in another order: a ray with an infinite inverse component fails
         // mask_cache_ray_ok, so a pass where every active ray passes is not `slow`; a pass where one fails takes the literal walk
-        // if it is slow and the generic MODE 1 walk otherwise (below, whether its signs are uniform or not).
+        // if it is slow and the generic MODE 1 walk otherwise (whether its signs are uniform or not).
+        auto cached = [&](const uint32_t oct) -> bool {  // false: a list did not fit the arena in mid-walk
+            switch (oct) {
+                case 0: return trace_packet_cached<0>(sc, r, active, hit, mc.lds);
+                case 1: return trace_packet_cached<1>(sc, r, active, hit, mc.lds);
+                case 2: return trace_packet_cached<2>(sc, r, active, hit, mc.lds);
+                case 3: return trace_packet_cached<3>(sc, r, active, hit, mc.lds);
+                case 4: return trace_packet_cached<4>(sc, r, active, hit, mc.lds);
+                case 5: return trace_packet_cached<5>(sc, r, active, hit, mc.lds);
+                case 6: return trace_packet_cached<6>(sc, r, active, hit, mc.lds);
+                default: return trace_packet_cached<7>(sc, r, active, hit, mc.lds);
+            }
+        };
+#ifndef MP_NO_ENTRY_FOLD
+        // One bounds test first (mask_cache.h, mask_cache_pass_inside, with the argument): a pass whose every active ray lies inside
+        // a valid B needs none of the guards in the block below -- mask_cache_ray_ok, the infinite-inverse test, the sign ballots,
+        // mask_cache_begin_pass: all implied -- and enters the cached walk of B's pattern at once, B unchanged.  Any other pass (no
+        // valid B, a ray outside B, a NaN or infinite component, mixed signs) goes through the block as before.
+        // -DMP_NO_ENTRY_FOLD: the block for every pass (A/B builds, tools/build_variant.sh).
+        uint32_t oct = sc.boxes_ordered ? mask_cache_pass_inside(mc, r, active) : kNoPattern;
+        if (oct != kNoPattern) MP_PROF_COUNT(10);
+        if (oct == kNoPattern) {
+            if (__ballot(active & !mask_cache_ray_ok(r)) != 0) {
+                const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
+                if (__ballot(slow) != 0) trace_packet_impl<2, -1>(sc, r, active, st, hit);
+                else trace_packet_impl<1, -1>(sc, r, active, st, hit);
+                return;
+            }
+            if (sc.boxes_ordered) {
+                const uint64_t am = __ballot(active);
+                const uint64_t nx = __ballot(active && r.ix < 0.0f), ny = __ballot(active && r.iy < 0.0f), nz = __ballot(active && r.iz < 0.0f);
+                if ((nx == 0 || nx == am) && (ny == 0 || ny == am) && (nz == 0 || nz == am)) {
+                    oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+                    mask_cache_begin_pass(mc, r, active, oct);
+                    MP_PROF_COUNT(11);
+                }
+            }
+        }
+        if (oct != kNoPattern && cached(oct)) return;
+#else
         if (__ballot(active & !mask_cache_ray_ok(r)) != 0) {
             const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
             if (__ballot(slow) != 0) trace_packet_impl<2, -1>(sc, r, active, st, hit);
             else trace_packet_impl<1, -1>(sc, r, active, st, hit);
             return;
         }
-    } else {
-        const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
-        if (__ballot(slow) != 0) {
-            trace_packet_impl<2, -1>(sc, r, active, st, hit);
-            return;
+        if (sc.boxes_ordered) {
+            const uint64_t am = __ballot(active);
+            const uint64_t nx = __ballot(active && r.ix < 0.0f), ny = __ballot(active && r.iy < 0.0f), nz = __ballot(active && r.iz < 0.0f);
+            if ((nx == 0 || nx == am) && (ny == 0 || ny == am) && (nz == 0 || nz == am)) {
+                const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
+                mask_cache_begin_pass(mc, r, active, oct);
+                MP_PROF_COUNT(11);
+                if (cached(oct)) return;
+            }
         }
+#endif
+        trace_packet_impl<1, -1>(sc, r, active, st, hit);  // (mixed signs, or a list did not fit: the generic walk, from the start)
+        return;
+    }
+    const bool slow = active && (fabsf(r.ix) == INFINITY || fabsf(r.iy) == INFINITY || fabsf(r.iz) == INFINITY);
+    if (__ballot(slow) != 0) {
+        trace_packet_impl<2, -1>(sc, r, active, st, hit);
+        return;
     }
     if (OCTANTS && sc.boxes_ordered) {
         const uint64_t am = __ballot(active);
         const uint64_t nx = __ballot(active && r.ix < 0.0f), ny = __ballot(active && r.iy < 0.0f), nz = __ballot(active && r.iz < 0.0f);
         if ((nx == 0 || nx == am) && (ny == 0 || ny == am) && (nz == 0 || nz == am)) {
-            const uint32_t oct = (nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u);
-            if (MC) {  // kernels with a mask cache: the sign-specialised walks use it
-                mask_cache_begin_pass(mc, r, active, oct);
-                bool done;
-                switch (oct) {
-                    case 0: done = trace_packet_cached<0>(sc, r, active, hit, mc.lds); break;
-                    case 1: done = trace_packet_cached<1>(sc, r, active, hit, mc.lds); break;
-                    case 2: done = trace_packet_cached<2>(sc, r, active, hit, mc.lds); break;
-                    case 3: done = trace_packet_cached<3>(sc, r, active, hit, mc.lds); break;
-                    case 4: done = trace_packet_cached<4>(sc, r, active, hit, mc.lds); break;
-                    case 5: done = trace_packet_cached<5>(sc, r, active, hit, mc.lds); break;
-                    case 6: done = trace_packet_cached<6>(sc, r, active, hit, mc.lds); break;
-                    default: done = trace_packet_cached<7>(sc, r, active, hit, mc.lds); break;
-                }
-                if (done) return;  // (else: a list did not fit the arena in mid-walk -- the generic walk below, from the start)
-            } else {
-                switch (oct) {
-                    case 0: trace_packet_impl<1, 0>(sc, r, active, st, hit); return;
-                    case 1: trace_packet_impl<1, 1>(sc, r, active, st, hit); return;
-                    case 2: trace_packet_impl<1, 2>(sc, r, active, st, hit); return;
-                    case 3: trace_packet_impl<1, 3>(sc, r, active, st, hit); return;
-                    case 4: trace_packet_impl<1, 4>(sc, r, active, st, hit); return;
-                    case 5: trace_packet_impl<1, 5>(sc, r, active, st, hit); return;
-                    case 6: trace_packet_impl<1, 6>(sc, r, active, st, hit); return;
-                    default: trace_packet_impl<1, 7>(sc, r, active, st, hit); return;
-                }
+            switch ((nx ? 1u : 0u) | (ny ? 2u : 0u) | (nz ? 4u : 0u)) {
+                case 0: trace_packet_impl<1, 0>(sc, r, active, st, hit); return;
+                case 1: trace_packet_impl<1, 1>(sc, r, active, st, hit); return;
+                case 2: trace_packet_impl<1, 2>(sc, r, active, st, hit); return;
+                case 3: trace_packet_impl<1, 3>(sc, r, active, st, hit); return;
+                case 4: trace_packet_impl<1, 4>(sc, r, active, st, hit); return;
+                case 5: trace_packet_impl<1, 5>(sc, r, active, st, hit); return;
+                case 6: trace_packet_impl<1, 6>(sc, r, active, st, hit); return;
+                default: trace_packet_impl<1, 7>(sc, r, active, st, hit); return;
             }
         }
     }

@@ -16,7 +16,7 @@
 
 namespace mp {
 namespace {
-__device__ unsigned long long g_prof[10];  // [0] list builds [1] leaf-mask builds [2] inner links followed (with -DMP_PROF_MASK_TRIS: triangles the built leaf masks keep, leaf_mask_slow) [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk [7] pops skipped on an empty-mask leaf [8] units that skip the per-ray scene pre-test [9] units that keep it
+__device__ unsigned long long g_prof[12];  // [0] list builds [1] leaf-mask builds [2] inner links followed (with -DMP_PROF_MASK_TRIS: triangles the built leaf masks keep, leaf_mask_slow) [3] bound sets [4] table evictions [5] arena resets [6] passes left to the uncached walk [7] pops skipped on an empty-mask leaf [8] units that skip the per-ray scene pre-test [9] units that keep it [10] passes that enter the cached walk on the one bounds test (packet_walk.h, trace_packet) [11] passes that enter it through the full guards
 static_assert(sizeof(g_prof) / sizeof(g_prof[0]) == kProfSlots, "family_launch.h's count of the slots");
 
 // host side: sum[i] += this unit's counter i, for all kProfSlots of them; reset != 0 zeroes the unit's counters afterwards
