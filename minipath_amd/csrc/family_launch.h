@@ -33,7 +33,7 @@ int launch_rays(QueryKind kind, const DevScene& sc, const float* ox, const float
                 std::string& err);
 #ifdef MP_PROF_MISSES
 // counted builds (prof_counters.h): each unit that runs the cached packet walk adds its copy of the counters to sum[0 .. kProfSlots)
-// and, with reset != 0, zeroes it; mp_prof_read* (kernels.hip) report the sum
+// and, with reset != 0, zeroes it; mp_prof_read_n (kernels.hip) reports the sum
 constexpr int kProfSlots = 12;
 int prof_add_tiles(unsigned long long* sum, int reset);
 int prof_add_aov(unsigned long long* sum, int reset);

@@ -200,8 +200,8 @@ int launch_quantise(const float* d_rgba_f32, uint8_t* d_rgba_u8, uint64_t n_pixe
 }  // namespace mp
 
 #ifdef MP_PROF_MISSES
-// the first n counters (n <= 10: every slot), summed over the units that run the cached walk, each of which counts into a copy of
-// its own (prof_counters.h); reset != 0 zeroes all of them, in every unit, afterwards
+// the first n counters (n <= kProfSlots, family_launch.h: every slot), summed over the units that run the cached walk, each of which counts
+// into a copy of its own (prof_counters.h); reset != 0 zeroes all of them, in every unit, afterwards
 extern "C" int mp_prof_read_n(unsigned long long* out, int n, int reset) {
     if (n < 0 || n > mp::kProfSlots) return 1;
     unsigned long long sum[mp::kProfSlots] = {};
@@ -212,7 +212,4 @@ extern "C" int mp_prof_read_n(unsigned long long* out, int n, int reset) {
     for (int i = 0; i < n; i++) out[i] = sum[i];
     return 0;
 }
-// (the entry points from before the counters grew: the first eight, the first four)
-extern "C" int mp_prof_read8(unsigned long long* out, int reset) { return mp_prof_read_n(out, 8, reset); }
-extern "C" int mp_prof_read(unsigned long long* out, int reset) { return mp_prof_read_n(out, 4, reset); }
 #endif

@@ -11,23 +11,26 @@
       wide     the stand-in through a lens 2.5 m across
       vertex   the stand-in with the eye exactly on a vertex of the mesh (u, v, t = +-0 at the triangles that share it)
 (c) The same frames in two counted builds of the library (minipath_amd/csrc/Makefile: maskfar, the shipped rule, and nomaskfar,
-    -DMP_NO_MASK_FAR; both -DMP_PROF_MISSES -DMP_PROF_MASK_TRIS, so slot 1 of mp_prof_read_n is the number of leaf-mask builds and slot 2
-    the number of triangles those masks keep), each in a process of its own: both give the oracle's bits, and the masks of the shipped
-    rule keep strictly fewer triangles per build.
-
-Run as a program (MINIPATH_HIP_SO is read when the package loads) this file renders the counted frames and writes them to the .npz
-named."""
+    -DMP_NO_MASK_FAR; both -DMP_PROF_MISSES -DMP_PROF_MASK_TRIS, so `leaf_mask_builds` is the number of leaf-mask builds and the slot
+    after it, `inner_links` in other builds, the number of triangles those masks keep), each in a process of its own
+    (tests/walk_frames.py, run_in_variant): both give the oracle's bits, and the masks of the shipped rule keep strictly fewer
+    triangles per build."""
 import ctypes as C
 import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import minipath_amd as mp
+from minipath_amd import _lib
+from tests import aov_model
+from tests import graft_model as gm
+from tests import walk_frames as wf
+from tests.walk_frames import CSRC, Counters, assert_same_bits, differing, frame, planes, run_in_variant
+
+pytestmark = pytest.mark.gpu
+PROBE = os.path.join(CSRC, "libmp_mask_probe.so")
 
 RES, TS, SPP, AOV_SPP = (96, 64), 32, 64, 32
 SEED = 41
@@ -41,8 +44,6 @@ NCASES = 1 << 18
 def vertex_eye():
     """a vertex of the stand-in's mesh all of whose coordinates are of magnitude >= 1 (the pinhole's lens offset rounds away, so every
     ray starts on it), and a point to look at"""
-    from tests import graft_model as gm
-
     p = gm.evict_mesh()[0].reshape(-1, 3)
     ok = np.nonzero(np.all(np.abs(p) >= 1.0, axis=1))[0]
     v = p[ok[len(ok) // 2]]
@@ -50,63 +51,28 @@ def vertex_eye():
 
 
 def cameras():
-    import minipath_amd as mp
-    from minipath_amd import scenes
-
     eye, at = vertex_eye()
-    return {"teapot": mp.Camera.teapot_view(),
-            "atrium": scenes.atrium_camera(),
-            "wide": scenes.atrium_camera().f_number(0.01),
-            "vertex": mp.Camera.default().look_at(eye, at, (0.0, 1.0, 0.0)).f_number(1e30)}
+    return {**wf.cameras(), "vertex": mp.Camera.default().look_at(eye, at, (0.0, 1.0, 0.0)).f_number(1e30)}
 
 
 def make_objects(ctx):
-    import minipath_amd as mp
-    from tests import graft_model as gm
-    from tests.conftest import TEAPOT
-
-    atrium = mp.TriangleBvh.build(*gm.evict_mesh(), ctx)
-    return {"teapot": mp.TriangleBvh.with_obj(TEAPOT, ctx), "atrium": atrium, "wide": atrium, "vertex": atrium}
+    out = wf.make_objects(ctx, SCENES)
+    out["vertex"] = out["atrium"]
+    return out
 
 
 def counted_frames():
     """{name: f32 frame, name + "_masks": (leaf-mask builds, triangles the built masks keep)} in the library that is loaded"""
-    import torch
-
-    import minipath_amd as mp
-    from minipath_amd import _lib
-    from tests.unit_list_frames import frame
-
-    lib = _lib.lib()
-    lib.mp_prof_read_n.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
+    prof = Counters(_lib.lib())
     ctx = mp.Context(0)
     cams, objs, out = cameras(), make_objects(ctx), {}
     for name in SCENES:
-        cnt = (C.c_ulonglong * 10)()
-        assert lib.mp_prof_read_n(cnt, 10, 1) == 0  # reset
+        prof.reset()
         f, _, names, _ = frame(ctx, objs[name], cams[name], mp.RenderSettings(TS, SPP, RES, seed=SEED))
         assert names == [PACKET], names
-        torch.cuda.synchronize()
-        assert lib.mp_prof_read_n(cnt, 10, 0) == 0
-        out[name], out[name + "_masks"] = f, np.array([cnt[1], cnt[2]], np.uint64)
+        c = prof.read()
+        out[name], out[name + "_masks"] = f, np.array([c["leaf_mask_builds"], c["inner_links"]], np.uint64)  # (-DMP_PROF_MASK_TRIS: triangles kept)
     return out
-
-
-if __name__ == "__main__":
-    np.savez(sys.argv[1], **counted_frames())
-    sys.exit(0)
-
-import pytest  # noqa: E402
-
-import minipath_amd as mp  # noqa: E402
-from tests import aov_model  # noqa: E402
-from tests import graft_model as gm  # noqa: E402
-from tests.conftest import TEAPOT  # noqa: E402
-from tests.unit_list_frames import bits, frame, planes  # noqa: E402
-
-pytestmark = pytest.mark.gpu
-CSRC = os.path.join(ROOT, "minipath_amd", "csrc")
-PROBE = os.path.join(CSRC, "libmp_mask_probe.so")
 
 
 def test_probe_beyond_the_far_edges():
@@ -133,17 +99,16 @@ def test_probe_beyond_the_far_edges():
     assert o[3] > 0 and o[4] > o[5]
 
 
-@functools.lru_cache(maxsize=None)
 def oracle_scene(oracle, name):
-    return oracle.Bvh.from_obj(TEAPOT) if name == "teapot" else gm.evict_oracle(oracle)
+    return wf.oracle_scene(oracle, "atrium" if name == "vertex" else name)
 
 
 @functools.lru_cache(maxsize=None)
 def wanted(oracle, name):
     """the oracle's frame of a scene, once: (f32, u8)"""
-    smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
-    f, u8, *_ = oracle_scene(oracle, name).render_image_mt(smp, *RES, SPP, SEED, TS, 16)
-    return f, u8
+    if name != "vertex":
+        return wf.oracle_frame(oracle, name, RES, SPP, SEED, TS)
+    return wf.oracle_image(oracle, oracle_scene(oracle, name), cameras()[name], RES, SPP, SEED, TS)
 
 
 @pytest.fixture(scope="module")
@@ -171,9 +136,8 @@ def test_frame_matches_the_oracle(oracle, world, name):
     check_view(name, of)
     f, u8, names, _ = frame(ctx, objs[name], cameras()[name], mp.RenderSettings(TS, SPP, RES, seed=SEED))
     assert names == [PACKET], names
-    diff = int(np.sum(bits(f) != bits(of)))
-    print(f"{name}: {names}, {diff} of {of.size} values differ from the oracle")
-    assert f.shape == of.shape and diff == 0, (name, diff)
+    print(f"{name}: {names}, {differing(f, of)} of {of.size} values differ from the oracle")
+    assert_same_bits(f, of, name)
     assert np.array_equal(u8, ou8), name
 
 
@@ -185,30 +149,16 @@ def test_planes_match_the_model(oracle, world, name):
     smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
     want = aov_model.planes(oracle, oracle_scene(oracle, name).intersect, smp, RES[0], AOV_SPP, SEED, (0, 0, *RES))
     for k in WHICH:
-        diff = int(np.sum(bits(img[k]) != bits(want[k])))
-        print(f"{name} {k}: {diff} of {want[k].size} values differ from the model")
-        assert img[k].shape == want[k].shape and diff == 0, (name, k, diff)
-
-
-def _counted(tmp_path, variant):
-    so = os.path.join(CSRC, f"libminipath_hip_{variant}.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / f"{variant}.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(dst) as z:
-        return {k: z[k] for k in z.files}
+        print(f"{name} {k}: {differing(img[k], want[k])} of {want[k].size} values differ from the model")
+        assert_same_bits(img[k], want[k], (name, k))
 
 
 def test_masks_keep_fewer_triangles_than_without_the_far_side(oracle, tmp_path):
-    on, off = _counted(tmp_path, "maskfar"), _counted(tmp_path, "nomaskfar")
+    on, off = (run_in_variant(v, "tests.test_mask_far_side_gpu:counted_frames", tmp_path, timeout=600) for v in ("maskfar", "nomaskfar"))
     for name in SCENES:
         of = wanted(oracle, name)[0]
-        assert np.array_equal(bits(on[name]), bits(of)), name
-        assert np.array_equal(bits(off[name]), bits(of)), name
+        assert_same_bits(on[name], of, ("maskfar", name))
+        assert_same_bits(off[name], of, ("nomaskfar", name))
         (b1, k1), (b0, k0) = (int(v) for v in on[name + "_masks"]), (int(v) for v in off[name + "_masks"])
         print(f"{name}: leaf-mask builds {b1} / {b0}, triangles kept {k1} / {k0}: per build {k1 / max(b1, 1):.2f} with the far side, "
               f"{k0 / max(b0, 1):.2f} without")

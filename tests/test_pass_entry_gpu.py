@@ -13,35 +13,24 @@ the sign ballots and mask_cache_begin_pass; every other pass takes the full rout
   2.5 m across, whose units decline to set bounds from their corner rays or leave them (an invalid header at the first pass,
   escapes and mixed signs after).
 * The same three frames in the counted build libminipath_hip_noskip.so (-DMP_PROF_MISSES; its own switch concerns the walk, not the
-  entry), in a process of its own: slots 10 and 11 of mp_prof_read_n are the passes that enter the cached walk on the one bounds
-  test and those that enter it through the full guards.  A unit has four passes here, so both are bounded by 4 x units.  The teapot:
+  entry), in a process of its own (tests/walk_frames.py, run_in_variant): `passes_bounds_entry` and `passes_full_entry` are the passes that
+  enter the cached walk on the one bounds test and those that enter it through the full guards.  A unit has four passes here, so both are bounded by 4 x units.  The teapot:
   its units set B from their corner rays, so passes that reach the walk find themselves inside B: the short route occurs.  The
   wide lens: units that decline to set B send their first pass through the full guards, which sets B with a quarter of its extent
-  to spare, so both routes occur.  The camera turned away: the per-ray pre-test stops every pass before the walk, neither occurs.
-
-Run as a program (MINIPATH_HIP_SO is read when the package loads) this file renders the counted frames and writes them to the .npz
-named."""
+  to spare, so both routes occur.  The camera turned away: the per-ray pre-test stops every pass before the walk, neither occurs."""
 import ctypes as C
-import functools
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
 import minipath_amd as mp
-from tests import graft_model as gm
-from tests.conftest import TEAPOT
-from tests.unit_list_frames import bits, frame
+from minipath_amd import _lib
+from tests.walk_frames import CSRC, Counters, assert_same_bits, cameras, differing, frame, make_objects, oracle_frame, run_in_variant
 
 pytestmark = pytest.mark.gpu
 
-SO = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "minipath_amd", "csrc", "libmp_mask_probe.so")
+SO = os.path.join(CSRC, "libmp_mask_probe.so")
 STATE, NO = 12, 8  # the header's state dword; "no pattern"
 LO = {0: 0, 1: 6, 2: 13}  # header slot of group g's minima (origin, inverse direction, direction); the maxima follow at + 3
 F = np.float32
@@ -197,22 +186,7 @@ def test_entry_decision_equals_its_definition():
 # ---- frames ---------------------------------------------------------------------------------------------------------------------------
 RES, TS, SPP, SEED = (96, 64), 32, 64, 57
 PACKET = "render_tiles_packet_kernel<16, false, 8, false, true>"
-
-
-def cameras():
-    from minipath_amd import scenes
-
-    return {"teapot": mp.Camera.teapot_view(),
-            "away": mp.Camera.default().look_at((0.0, 2.0, 10.0), (0.0, 2.5, 20.0), (0.0, 1.0, 0.0)).f_number(4.8),
-            "wide": scenes.atrium_camera().f_number(0.01)}
-
-
-@functools.lru_cache(maxsize=None)
-def oracle_frame(oracle, name):
-    twin = gm.evict_oracle(oracle) if name == "wide" else oracle.Bvh.from_obj(TEAPOT)
-    smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
-    f, u8, *_ = twin.render_image_mt(smp, *RES, SPP, SEED, TS, 16)
-    return f, u8
+VIEWS = ("teapot", "away", "wide")
 
 
 @pytest.fixture(scope="module")
@@ -221,14 +195,13 @@ def world():
 
     assert torch.cuda.is_available(), "gpu tests need a GPU"
     ctx = mp.Context(0)
-    teapot = mp.TriangleBvh.with_obj(TEAPOT, ctx)
-    return ctx, {"teapot": teapot, "away": teapot, "wide": mp.TriangleBvh.build(*gm.evict_mesh(), ctx)}
+    return ctx, make_objects(ctx, VIEWS)
 
 
-@pytest.mark.parametrize("name", ["teapot", "away", "wide"])
+@pytest.mark.parametrize("name", VIEWS)
 def test_frame_matches_the_oracle(oracle, world, name):
     ctx, objs = world
-    of, ou8 = oracle_frame(oracle, name)
+    of, ou8 = oracle_frame(oracle, name, RES, SPP, SEED, TS)
     alpha = of[..., 3]
     if name == "teapot":
         assert 0.0 < alpha.mean() < 1.0
@@ -238,49 +211,30 @@ def test_frame_matches_the_oracle(oracle, world, name):
         assert np.count_nonzero(alpha) > alpha.size // 2
     f, u8, names, _ = frame(ctx, objs[name], cameras()[name], mp.RenderSettings(TS, SPP, RES, seed=SEED))
     assert names == [PACKET], names
-    diff = int(np.sum(bits(f) != bits(of)))
-    print(f"{name}: {diff} of {of.size} values differ from the oracle")
-    assert f.shape == of.shape and diff == 0, (name, diff)
+    print(f"{name}: {differing(f, of)} of {of.size} values differ from the oracle")
+    assert_same_bits(f, of, name)
     assert np.array_equal(u8, ou8), name
 
 
 def counted_frames():
     """{name: f32 frame, name + "_routes": (passes on the one bounds test, passes through the full guards)} in the library that is loaded"""
-    import torch
-
-    from minipath_amd import _lib
-
-    lib = _lib.lib()
-    lib.mp_prof_read_n.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
+    prof = Counters(_lib.lib())
     ctx = mp.Context(0)
-    teapot = mp.TriangleBvh.with_obj(TEAPOT, ctx)
-    objs = {"teapot": teapot, "away": teapot, "wide": mp.TriangleBvh.build(*gm.evict_mesh(), ctx)}
-    out = {}
-    for name, cam in cameras().items():
-        cnt = (C.c_ulonglong * 12)()
-        assert lib.mp_prof_read_n(cnt, 12, 1) == 0  # reset
-        f, _, names, _ = frame(ctx, objs[name], cam, mp.RenderSettings(TS, SPP, RES, seed=SEED))
+    cams, objs, out = cameras(), make_objects(ctx, VIEWS), {}
+    for name in VIEWS:
+        prof.reset()
+        f, _, names, _ = frame(ctx, objs[name], cams[name], mp.RenderSettings(TS, SPP, RES, seed=SEED))
         assert names == [PACKET], names
-        torch.cuda.synchronize()
-        assert lib.mp_prof_read_n(cnt, 12, 0) == 0
-        out[name], out[name + "_routes"] = f, np.array([cnt[10], cnt[11]], np.uint64)
+        c = prof.read()
+        out[name], out[name + "_routes"] = f, np.array([c["passes_bounds_entry"], c["passes_full_entry"]], np.uint64)
     return out
 
 
 def test_both_entry_routes_occur(oracle, tmp_path):
-    so = os.path.join(os.path.dirname(SO), "libminipath_hip_noskip.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / "frames.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(dst) as z:
-        got = {k: z[k] for k in z.files}
+    got = run_in_variant("noskip", "tests.test_pass_entry_gpu:counted_frames", tmp_path, timeout=600)
     passes = (RES[0] // 2) * (RES[1] // 2) * (SPP // 16)
-    for name in ("teapot", "away", "wide"):
-        assert np.array_equal(bits(got[name]), bits(oracle_frame(oracle, name)[0])), name
+    for name in VIEWS:
+        assert_same_bits(got[name], oracle_frame(oracle, name, RES, SPP, SEED, TS)[0], name)
         short, full = (int(v) for v in got[name + "_routes"])
         print(f"{name}: {short} passes enter on the one bounds test, {full} through the full guards, of {passes}")
         assert short + full <= passes, name
@@ -288,8 +242,3 @@ def test_both_entry_routes_occur(oracle, tmp_path):
     short, full = (int(v) for v in got["wide_routes"])
     assert short > 0 and full > 0, "both routes in the wide lens's frame"
     assert not got["away_routes"].any(), "a pass that the pre-test stops entered the walk"
-
-
-if __name__ == "__main__":
-    np.savez(sys.argv[1], **counted_frames())
-    sys.exit(0)

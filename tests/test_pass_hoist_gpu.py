@@ -12,22 +12,22 @@ render_aov_packet_kernel<4, ..., true>:
   sphere, group   a Sphere scene and an object group, on kernels this change leaves as they were
 
 The teapot, away and wide frames once more in the counted build libminipath_hip_noskip.so (-DMP_PROF_MISSES; the build's own switch,
--DMP_NO_EMPTY_SKIP, concerns the walk, not the pass entry), in a process of its own: slots 8 and 9 of mp_prof_read_n are the units whose passes
-skip the per-ray pre-test and the units that keep it.  The teapot's frame and the wide lens's must show both, the frame that looks away only the second.
-
-Run as a program (MINIPATH_HIP_SO is read when the package loads) this file renders the counted frames and writes them to the .npz
-named."""
-import ctypes as C
+-DMP_NO_EMPTY_SKIP, concerns the walk, not the pass entry), in a process of its own (tests/walk_frames.py, run_in_variant): `units_skip_pretest`
+and `units_keep_pretest` are the units whose passes skip the per-ray pre-test and the units that keep it.  The teapot's frame and the wide
+lens's must show both, the frame that looks away only the second."""
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import minipath_amd as mp
+from minipath_amd import _lib
+from tests import aov_model
+from tests import walk_frames as wf
+from tests.conftest import TEAPOT
+from tests.walk_frames import Counters, assert_same_bits, differing, frame, planes, run_in_variant
+
+pytestmark = pytest.mark.gpu
 
 RES, TS, SPP, AOV_SPP = (96, 64), 32, 64, 32
 SEED = 33
@@ -36,86 +36,35 @@ PACKET = "render_tiles_packet_kernel<16, false, 8, false, true>"
 AOV = "render_aov_packet_kernel<4, false, 8, false, true>"
 BALL = ((0.4, 0.0, 0.0), 1.0)
 GROUP_AT = [[0.0, 0.0, 0.0], [0.0, 3.5, -1.0]]
+CACHED = ("teapot", "atrium", "away", "wide")
 
 
 def cameras():
-    import minipath_amd as mp
-    from minipath_amd import scenes
-
-    eye = (0.0, 2.0, 10.0)  # Camera.teapot_view's
-    return {"teapot": mp.Camera.teapot_view(),
-            "atrium": scenes.atrium_camera(),
-            "away": mp.Camera.default().look_at(eye, (0.0, 2.5, 20.0), (0.0, 1.0, 0.0)).f_number(4.8),
-            "wide": scenes.atrium_camera().f_number(0.01),
+    return {**wf.cameras(),
             "sphere": mp.Camera.default().look_at((0.4, 5.0, 4.5), (0.0, 0.0, 0.0), (0, 1, 0)),
             "group": mp.Camera.default().look_at((1.0, 5.0, 12.0), (0.0, 2.0, 0.0), (0, 1, 0))}
 
 
-def make_objects(ctx, names):
-    import minipath_amd as mp
-    from tests import graft_model as gm
-    from tests.conftest import TEAPOT
-
-    out = {}
-    if {"teapot", "away", "group"} & set(names):
-        out["teapot"] = out["away"] = mp.TriangleBvh.with_obj(TEAPOT, ctx)
-    if {"atrium", "wide"} & set(names):
-        out["atrium"] = out["wide"] = mp.TriangleBvh.build(*gm.evict_mesh(), ctx)
-    if "sphere" in names:
-        out["sphere"] = mp.Sphere(*BALL, ctx)
-    if "group" in names:
-        out["group"] = mp.ObjectGroup([out["teapot"], mp.Sphere(*BALL, ctx)], np.array(GROUP_AT, np.float32))
-    return out
-
-
 def counted_frames():
     """{name: f32 frame, name + "_units": (units that skip the per-ray pre-test, units that keep it)} in the library that is loaded"""
-    import torch
-
-    import minipath_amd as mp
-    from minipath_amd import _lib
-    from tests.unit_list_frames import frame
-
-    lib = _lib.lib()
-    lib.mp_prof_read_n.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
+    prof = Counters(_lib.lib())
     ctx = mp.Context(0)
     cams, out = cameras(), {}
-    objs = make_objects(ctx, ("teapot", "away", "wide"))
+    objs = wf.make_objects(ctx, ("teapot", "away", "wide"))
     for name in ("teapot", "away", "wide"):
-        cnt = (C.c_ulonglong * 10)()
-        assert lib.mp_prof_read_n(cnt, 10, 1) == 0  # reset
+        prof.reset()
         f, _, names, _ = frame(ctx, objs[name], cams[name], mp.RenderSettings(TS, SPP, RES, seed=SEED))
         assert names == [PACKET], names
-        torch.cuda.synchronize()
-        assert lib.mp_prof_read_n(cnt, 10, 0) == 0
-        out[name], out[name + "_units"] = f, np.array([cnt[8], cnt[9]], np.uint64)  # units that skip the per-ray pre-test, that keep it
+        c = prof.read()
+        out[name], out[name + "_units"] = f, np.array([c["units_skip_pretest"], c["units_keep_pretest"]], np.uint64)
     return out
-
-
-if __name__ == "__main__":
-    np.savez(sys.argv[1], **counted_frames())
-    sys.exit(0)
-
-import pytest  # noqa: E402
-
-import minipath_amd as mp  # noqa: E402
-from tests import aov_model  # noqa: E402
-from tests import graft_model as gm  # noqa: E402
-from tests.conftest import TEAPOT  # noqa: E402
-from tests.unit_list_frames import bits, frame, planes  # noqa: E402
-
-pytestmark = pytest.mark.gpu
-CSRC = os.path.join(ROOT, "minipath_amd", "csrc")
-CACHED = ("teapot", "atrium", "away", "wide")
 
 
 @functools.lru_cache(maxsize=None)
 def oracle_scene(oracle, name):
     """the oracle's twin of a scene: a Bvh, or the sphere as (center, radius)"""
-    if name in ("teapot", "away"):
-        return oracle.Bvh.from_obj(TEAPOT)
-    if name in ("atrium", "wide"):
-        return gm.evict_oracle(oracle)
+    if name in CACHED:
+        return wf.oracle_scene(oracle, name)
     if name == "sphere":
         return BALL
     box = oracle.Bvh.from_obj(TEAPOT)
@@ -126,12 +75,12 @@ def oracle_scene(oracle, name):
 @functools.lru_cache(maxsize=None)
 def wanted(oracle, name):
     """the oracle's frame of a case, once: (f32, u8)"""
-    smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
-    twin = oracle_scene(oracle, name)
+    if name in CACHED:
+        return wf.oracle_frame(oracle, name, RES, SPP, SEED, TS)
     if name == "sphere":
-        return oracle.render_tile_sphere(*twin, smp, RES[0], SPP, SEED, 0, 0, *RES)
-    f, u8, *_ = twin.render_image_mt(smp, *RES, SPP, SEED, TS, 16)
-    return f, u8
+        smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
+        return oracle.render_tile_sphere(*BALL, smp, RES[0], SPP, SEED, 0, 0, *RES)
+    return wf.oracle_image(oracle, oracle_scene(oracle, name), cameras()[name], RES, SPP, SEED, TS)
 
 
 @pytest.fixture(scope="module")
@@ -140,7 +89,10 @@ def world():
 
     assert torch.cuda.is_available(), "gpu tests need a GPU"
     ctx = mp.Context(0)
-    return ctx, make_objects(ctx, CACHED + ("sphere", "group"))
+    objs = wf.make_objects(ctx, CACHED)
+    objs["sphere"] = mp.Sphere(*BALL, ctx)
+    objs["group"] = mp.ObjectGroup([objs["teapot"], mp.Sphere(*BALL, ctx)], np.array(GROUP_AT, np.float32))
+    return ctx, objs
 
 
 def check_view(name, f):
@@ -168,9 +120,8 @@ def test_frame_matches_the_oracle(oracle, world, name):
         assert names == [PACKET], names
     else:
         assert len(names) == 1 and names[0].count(",") < 4, names  # (the cached instantiations are the ones with five arguments)
-    diff = int(np.sum(bits(f) != bits(of)))
-    print(f"{name}: {names}, {diff} of {of.size} values differ from the oracle")
-    assert f.shape == of.shape and diff == 0, (name, diff)
+    print(f"{name}: {names}, {differing(f, of)} of {of.size} values differ from the oracle")
+    assert_same_bits(f, of, name)
     assert np.array_equal(u8, ou8), name
 
 
@@ -182,25 +133,15 @@ def test_planes_match_the_model(oracle, world, name):
     smp = oracle.sampler_from_array(cameras()[name].build_sampler(RES).as_array())
     want = aov_model.planes(oracle, oracle_scene(oracle, name).intersect, smp, RES[0], AOV_SPP, SEED, (0, 0, *RES))
     for k in WHICH:
-        diff = int(np.sum(bits(img[k]) != bits(want[k])))
-        print(f"{name} {k}: {diff} of {want[k].size} values differ from the model")
-        assert img[k].shape == want[k].shape and diff == 0, (name, k, diff)
+        print(f"{name} {k}: {differing(img[k], want[k])} of {want[k].size} values differ from the model")
+        assert_same_bits(img[k], want[k], (name, k))
 
 
 def test_both_outcomes_of_the_unit_pretest_occur(oracle, tmp_path):
-    so = os.path.join(CSRC, "libminipath_hip_noskip.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / "frames.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(dst) as z:
-        got = {k: z[k] for k in z.files}
+    got = run_in_variant("noskip", "tests.test_pass_hoist_gpu:counted_frames", tmp_path, timeout=600)
     units = (RES[0] // 2) * (RES[1] // 2)
     for name in ("teapot", "away", "wide"):
-        assert np.array_equal(bits(got[name]), bits(wanted(oracle, name)[0])), name
+        assert_same_bits(got[name], wanted(oracle, name)[0], name)
         skip, keep = (int(v) for v in got[name + "_units"])
         print(f"{name}: {skip} units skip the per-ray pre-test, {keep} keep it")
         assert skip + keep == units, name

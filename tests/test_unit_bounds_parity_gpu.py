@@ -7,18 +7,19 @@ bounds still hold every ray counted -- they bound the lens disc by its square --
 its bound sets (MP_PROF_MISSES): the test asserts more than 1.5 per unit on a frame of the interior view, where the shipped
 margin has 1.00 -- every unit adopts once, and a B of half the corners' extent cannot hold a pass of 64 rays spread over it.
 
-Each build renders in a process of its own (MINIPATH_HIP_SO is read when the package loads); run as a program this file is that
-process: it renders the cases and writes them to the .npz it is given."""
+Each build renders in a process of its own (tests/walk_frames.py, run_in_variant), which calls variant_frames."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import minipath_amd as mp
+from minipath_amd import _lib, scenes
+from tests.conftest import TEAPOT
+from tests.dispatch_cases import launched
+from tests.walk_frames import Counters, assert_same_bits, counted, run_in_variant
+
+pytestmark = pytest.mark.gpu
 
 RES, TILE, SEED = (96, 64), 32, 0x5EED
 SPPS = (16, 64, 256)
@@ -29,16 +30,11 @@ VIEWS = {  # name -> scene, eye, look-at, f-number (None: the teapot view's own 
     "pinhole": ("teapot", None, None, 1e9),
     "f/0.7": ("atrium", (-14.0, 4.5, 1.0), (10.0, 5.0, -2.0), 0.7),
 }
-TEAPOT = os.path.join(ROOT, "tests", "golden", "teapot.obj")
 
 
 def render_all(modes):
     """{f"{view}/{spp}/{mode}": image} with this process's library"""
     import torch
-
-    import minipath_amd as mp
-    from minipath_amd import scenes
-    from tests.dispatch_cases import launched
 
     out = {}
     for mode in modes:
@@ -60,46 +56,32 @@ def render_all(modes):
 
 def bound_sets_per_unit():
     """bound (re)sets per work unit of one frame of the interior view at 64 spp, in a build that counts them; None in others"""
-    import torch
-
-    import minipath_amd as mp
-    from minipath_amd import _lib, scenes
-    from tests.dispatch_cases import launched
-
     lib = _lib.lib()
-    if not hasattr(lib, "mp_prof_read"):
+    if not counted(lib):
         return None
-    lib.mp_prof_read.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    prof = Counters(lib)
     c = mp.Context(0)
     scene = mp.Scene(mp.TriangleBvh.build(*scenes.atrium(1, ATRIUM_DETAIL), c))
     _, eye, at, fnum = VIEWS["atrium"]
     fr = mp.FrameRenderer(scene, mp.Camera.default().look_at(eye, at, (0, 1, 0)).f_number(fnum), mp.RenderSettings(TILE, 64, RES, seed=SEED))
-    out = (C.c_ulonglong * 4)()
-    assert lib.mp_prof_read(out, 1) == 0
+    prof.reset()
     fr.render()
-    torch.cuda.synchronize()
-    assert lib.mp_prof_read(out, 0) == 0
+    sets = prof.read()["bound_sets"]
     in_flight = int(launched(c)[0].split("<")[1].split(",")[0])  # S samples of a pixel per pass: a unit is 64 / S pixels
-    return out[3] / (RES[0] * RES[1] * in_flight // 64)
+    return sets / (RES[0] * RES[1] * in_flight // 64)
 
 
-if __name__ == "__main__":
+def variant_frames():
+    """what a variant's process renders: the cases with the cache on, and the bound sets per unit where the build counts"""
     frames = render_all((1,))
     sets = bound_sets_per_unit()
     if sets is not None:
         frames["bound_sets_per_unit"] = np.float64(sets)
-    np.savez(sys.argv[1], **frames)
-    sys.exit(0)
-
-import pytest  # noqa: E402
-
-pytestmark = pytest.mark.gpu
+    return frames
 
 
 @pytest.fixture(scope="module")
 def expected(oracle, teapot_oracle_bvh):
-    from minipath_amd import scenes
-
     orc = {"teapot": teapot_oracle_bvh, "atrium": oracle.Bvh.build(*scenes.atrium(1, ATRIUM_DETAIL))}
     exp = {}
     for name, (scene, eye, at, fnum) in VIEWS.items():
@@ -119,9 +101,7 @@ def expected(oracle, teapot_oracle_bvh):
 def compare(got, expected, what):
     assert len(got) >= len(expected)
     for key, img in got.items():
-        e = expected[key.rsplit("/", 1)[0]]
-        diff = int(np.sum(np.ascontiguousarray(img).view(np.uint32) != np.ascontiguousarray(e).view(np.uint32)))
-        assert diff == 0, f"{what} {key}: {diff} words differ from the oracle"
+        assert_same_bits(img, expected[key.rsplit("/", 1)[0]], f"{what} {key} against the oracle")
 
 
 def test_default_margin_cache_on_and_off(expected):
@@ -130,16 +110,9 @@ def test_default_margin_cache_on_and_off(expected):
 
 @pytest.mark.parametrize("variant", ["margin0", "shrunk"])
 def test_other_margins(expected, variant, tmp_path):
-    so = os.path.join(ROOT, "minipath_amd", "csrc", f"libminipath_hip_{variant}.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / "frames.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(dst) as z:
-        compare({k: z[k] for k in z.files if k != "bound_sets_per_unit"}, expected, f"{variant}, view/spp/cache")
-        if variant == "shrunk":
-            print(f"shrunk: {float(z['bound_sets_per_unit']):.3f} bound sets per unit")
-            assert float(z["bound_sets_per_unit"]) > 1.5, "the -1/4 build does not widen after adopting"
+    got = run_in_variant(variant, "tests.test_unit_bounds_parity_gpu:variant_frames", tmp_path, timeout=900)
+    sets = got.pop("bound_sets_per_unit", None)
+    compare(got, expected, f"{variant}, view/spp/cache")
+    if variant == "shrunk":
+        print(f"shrunk: {float(sets):.3f} bound sets per unit")
+        assert float(sets) > 1.5, "the -1/4 build does not widen after adopting"

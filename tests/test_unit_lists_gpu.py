@@ -15,31 +15,33 @@ B. Frames, bit-equal to the oracle, with the kernels named: the teapot at 16 and
    unit; the frame has 1 536 units of four passes).  That build once more for the counters themselves: the fused tiles, the feature
    planes and the fused paths are translation units with a copy of the counters each, and what the library reports is their sum.
 
-Run as a program (the variant's process: MINIPATH_HIP_SO is read when the package loads) this file renders that frame under both
-formats and writes the images and the counters to the .npz it is given; with `counters` before the file name, one teapot frame
-from each of the three units and the counters after each."""
+The variant's frames are rendered in a process of its own (tests/walk_frames.py, run_in_variant): render_variant renders that frame
+under both formats and returns the images and the counters; count_families one teapot frame from each of the three units and
+the counters after each."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
+import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import minipath_amd as mp
+from minipath_amd import _lib, scenes
+from tests import aov_model
+from tests import graft_model as gm
+from tests import unit_list_model as ul
+from tests.conftest import TEAPOT
+from tests.dispatch_cases import launched
+from tests.walk_frames import (CSRC, PROF_SLOTS, Counters, assert_same_bits, bits, check_formats, evict_oracle_image, frame, make_contexts, named, planes,
+                               run_in_variant, set_options, teapot_oracle)
+
+pytestmark = pytest.mark.gpu
+F = np.float32
 
 
-def render_variant(dst):
+def render_variant():
     import torch
 
-    import minipath_amd as mp
-    from minipath_amd import _lib, scenes
-    from tests import graft_model as gm
-    from tests.dispatch_cases import launched
-
-    lib = _lib.lib()
-    lib.mp_prof_read8.argtypes = [C.POINTER(C.c_ulonglong), C.c_int]
+    prof = Counters(_lib.lib())
     out = {}
     for slots in (16, 8):
         ctx = mp.Context(0)
@@ -47,74 +49,38 @@ def render_variant(dst):
         obj = mp.TriangleBvh.build(*gm.evict_mesh(), ctx)
         assert obj.device_tree(packet=True)[0].shape[1] == slots
         fr = mp.FrameRenderer(mp.Scene(obj), scenes.atrium_camera(), mp.RenderSettings(gm.EVICT_TS, 64, gm.EVICT_RES, seed=gm.EVICT_SEED))
-        cnt = (C.c_ulonglong * 8)()
-        assert lib.mp_prof_read8(cnt, 1) == 0
+        prof.reset()
         fr.render()
         names = launched(ctx)
         assert names == ["render_tiles_packet_kernel<16, false, 8, false, true>"], names
         img, _ = fr.untile()
         torch.cuda.synchronize()
-        assert lib.mp_prof_read8(cnt, 0) == 0
         out[f"image{slots}"] = img.cpu().numpy()
-        out[f"counters{slots}"] = np.array(list(cnt), np.uint64)
-    np.savez(dst, **out)
+        out[f"counters{slots}"] = np.array(list(prof.read().values()), np.uint64)
+    return out
 
 
-def count_families(dst):
+def count_families():
     """a counted build: one teapot frame from each unit that runs the cached walk (fused tiles, feature planes, fused paths), the
-    ten counters read -- summed over the units' copies -- after a reset and after every frame, then read with a reset and once more"""
-    import torch
+    counters read -- summed over the units' copies -- after a reset and after every frame, then read with a reset and once more"""
+    prof = Counters(_lib.lib())
 
-    import minipath_amd as mp
-    from minipath_amd import _lib
-    from tests.conftest import TEAPOT
-    from tests.unit_list_frames import frame, planes
-
-    lib = _lib.lib()
-    lib.mp_prof_read_n.argtypes = [C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
-
-    def read(reset):
-        cnt = (C.c_ulonglong * 10)()
-        torch.cuda.synchronize()
-        assert lib.mp_prof_read_n(cnt, 10, reset) == 0
-        return [int(v) for v in cnt]
+    def read(reset=False):
+        return list(prof.read(reset).values())
 
     ctx = mp.Context(0)
     obj = mp.TriangleBvh.with_obj(TEAPOT, ctx)
     cam, res, seed, ts = mp.Camera.teapot_view(), (64, 48), 21, 32
-    read(1)
-    rows, names = [read(0)], []
+    prof.reset()
+    rows, names = [read()], []
     names.append(frame(ctx, obj, cam, mp.RenderSettings(ts, 16, res, seed=seed))[2])
-    rows.append(read(0))
+    rows.append(read())
     names.append(planes(ctx, obj, cam, mp.RenderSettings(ts, 16, res, seed=seed), ("ids", "albedo", "normal"))[1])
-    rows.append(read(0))
+    rows.append(read())
     names.append(frame(ctx, obj, cam, mp.RenderSettings(ts, 32, res, seed=seed, max_depth=2))[2])
-    rows.append(read(0))
-    np.savez(dst, names=np.array(["\n".join(n) for n in names]), counters=np.array(rows, np.uint64), with_reset=np.array(read(1), np.uint64),
-             after_reset=np.array(read(0), np.uint64))
-
-
-if __name__ == "__main__":
-    if sys.argv[1] == "counters":
-        count_families(sys.argv[2])
-    else:
-        render_variant(sys.argv[1])
-    sys.exit(0)
-
-import pytest  # noqa: E402
-
-import minipath_amd as mp  # noqa: E402
-from minipath_amd import scenes  # noqa: E402
-from tests import aov_model  # noqa: E402
-from tests import dispatch_cases as dc  # noqa: E402
-from tests import graft_model as gm  # noqa: E402
-from tests import unit_list_model as ul  # noqa: E402
-from tests.conftest import TEAPOT  # noqa: E402
-from tests.unit_list_frames import bits, check_formats, evict_oracle_image, frame, make_contexts, planes, set_options, teapot_oracle  # noqa: E402
-
-pytestmark = pytest.mark.gpu
-F = np.float32
-CSRC = os.path.join(ROOT, "minipath_amd", "csrc")
+    rows.append(read())
+    return dict(names=np.array(["\n".join(n) for n in names]), counters=np.array(rows, np.uint64), with_reset=np.array(read(True), np.uint64),
+                after_reset=np.array(read(), np.uint64))
 
 
 # ---- A ---------------------------------------------------------------------------------------------------------------------------
@@ -277,8 +243,7 @@ def test_teapot_feature_plane_kernel(ctxs, oracle, spp, s_in_flight):
         img, names = planes(ctx, mp.TriangleBvh.with_obj(TEAPOT, ctx), mp.Camera.teapot_view(), mp.RenderSettings(ts, spp, res, seed=seed), which)
         assert names == [f"render_aov_packet_kernel<{s_in_flight}, false, 8, false, true>"], (slots, names)
         for k in which:
-            diff = int(np.sum(bits(img[k]) != bits(want[k])))
-            assert diff == 0, (slots, k, diff)
+            assert_same_bits(img[k], want[k], (slots, k))
         got[slots] = img
     for k in which:
         assert np.array_equal(bits(got[16][k]), bits(got[8][k]))
@@ -294,8 +259,8 @@ def test_teapot_path_kernel_cached_camera_pass(ctxs, oracle, spp, cached):
     for slots, ctx in ctxs.items():
         f, u8, names, seg = frame(ctx, mp.TriangleBvh.with_obj(TEAPOT, ctx), mp.Camera.teapot_view(), mp.RenderSettings(ts, spp, res, seed=seed, max_depth=depth))
         assert names == ["render_paths_kernel<8, false, false, true>" if cached else "render_paths_kernel<8, false, false>"], (slots, names)
-        diff = int(np.sum(bits(f) != bits(of)))
-        assert diff == 0 and np.array_equal(u8, ou8) and seg == oseg, (slots, diff)
+        assert_same_bits(f, of, slots)
+        assert np.array_equal(u8, ou8) and seg == oseg, slots
         got[slots] = f
     assert np.array_equal(bits(got[16]), bits(got[8]))
 
@@ -308,25 +273,17 @@ def test_atrium_frame_both_formats(ctxs, oracle):
 
 
 def test_atrium_frame_with_a_tiny_table_and_arena(oracle, tmp_path):
-    so = os.path.join(CSRC, "libminipath_hip_lists_tiny.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / "frames.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    got = run_in_variant("lists_tiny", "tests.test_unit_lists_gpu:render_variant", tmp_path, timeout=600)
     of, _ = evict_oracle_image(oracle, 64)
     units = gm.EVICT_RES[0] * gm.EVICT_RES[1] // 4
-    with np.load(dst) as z:
-        for slots in (16, 8):
-            diff = int(np.sum(bits(z[f"image{slots}"]) != bits(of)))
-            builds, _, links, _, evictions, resets, left, _ = (int(v) for v in z[f"counters{slots}"])
-            print(f"lists_tiny, {slots} slots: per unit {builds / units:.2f} list builds, {evictions / units:.2f} evictions, {resets / units:.2f} arena resets, "
-                  f"{left / units:.2f} passes left to the uncached walk; {links / (4 * units):.2f} inner links per pass")
-            assert diff == 0, (slots, diff)
-            assert evictions >= units * 0.21 / 4 and resets >= units * 0.53 / 4 and left >= units * 0.53 / 4, (slots, evictions, resets, left)
-            assert builds >= units and left <= resets
+    for slots in (16, 8):
+        c = named(got[f"counters{slots}"])
+        builds, evictions, resets, left = c["list_builds"], c["evictions"], c["arena_resets"], c["passes_left_uncached"]
+        print(f"lists_tiny, {slots} slots: per unit {builds / units:.2f} list builds, {evictions / units:.2f} evictions, {resets / units:.2f} arena resets, "
+              f"{left / units:.2f} passes left to the uncached walk; {c['inner_links'] / (4 * units):.2f} inner links per pass")
+        assert_same_bits(got[f"image{slots}"], of, slots)
+        assert evictions >= units * 0.21 / 4 and resets >= units * 0.53 / 4 and left >= units * 0.53 / 4, (slots, evictions, resets, left)
+        assert builds >= units and left <= resets
 
 
 def test_counters_are_summed_over_the_units_that_run_the_cached_walk(tmp_path):
@@ -335,21 +292,14 @@ def test_counters_are_summed_over_the_units_that_run_the_cached_walk(tmp_path):
     packet kernel and the feature planes at 16 spp, and a depth-2 path frame at 32 spp -- the fewest samples at which the plan names
     the path kernel's cached row (launch_plan.cpp; at 16 it names the row without a cache, which counts nothing).  Slot 0, list
     builds, grows with every frame: no unit's counters are lost.  Exact counts are the business of the tests above."""
-    so = os.path.join(CSRC, "libminipath_hip_lists_tiny.so")
-    if not os.path.exists(so):
-        pytest.fail(f"{so} missing: run build() first")
-    dst = str(tmp_path / "counters.npz")
-    flags = ["-s"] if sys.flags.no_user_site else []
-    r = subprocess.run([sys.executable, *flags, os.path.abspath(__file__), "counters", dst], env=dict(os.environ, MINIPATH_HIP_SO=so), cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    with np.load(dst) as z:
-        names = [n.split("\n") for n in z["names"]]
-        counters, with_reset, after_reset = z["counters"], z["with_reset"], z["after_reset"]
-    print("list builds after the reset and after each frame:", counters[:, 0].tolist())
+    got = run_in_variant("lists_tiny", "tests.test_unit_lists_gpu:count_families", tmp_path, timeout=600)
+    names = [n.split("\n") for n in got["names"]]
+    counters, with_reset, after_reset = got["counters"], got["with_reset"], got["after_reset"]
+    builds = counters[:, PROF_SLOTS.index("list_builds")]
+    print("list builds after the reset and after each frame:", builds.tolist())
     assert names == [["render_tiles_packet_kernel<4, false, 8, false, true>"], ["render_aov_packet_kernel<4, false, 8, false, true>"],
                      ["render_paths_kernel<8, false, false, true>"]], names
-    assert counters.shape == (4, 10) and not counters[0].any(), "all ten counters are zero after a reset"
-    assert counters[0, 0] < counters[1, 0] < counters[2, 0] < counters[3, 0], counters[:, 0]
+    assert counters.shape == (4, len(PROF_SLOTS)) and not counters[0].any(), "all the counters are zero after a reset"
+    assert builds[0] < builds[1] < builds[2] < builds[3], builds
     assert np.array_equal(with_reset, counters[3]), "a read with reset = 1 still reports what was counted"
     assert not after_reset.any(), "... and leaves every unit's copy at zero"
