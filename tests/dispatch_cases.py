@@ -18,6 +18,8 @@ frames of the matrix (72 x 40 and smaller) are all "small launches" there (units
 select 32 in flight.  On the GPU the 32-in-flight forms, <32, *, 8> included, are reached through that rule.  The plans' other
 two ways to them (`big && nspp >= 128`, and the cached table of a launch that is not small) need frames of 12 288 work units or
 more, whose oracle renders do not fit a test; tests/test_launch_plan_cpu.py pins both by name on the benchmark's own frame.
+At these sizes every launch is also one work unit per wave: the frames on which the waves of the persistent kernels run many
+units in a row are those of tests/long_waves.py (the context option blocks_per_cu = 1, tests/test_gpu_long_waves.py).
 
 The matrix's own tiling is regular: at tile sizes 32 and 16 the clipped column and row of its frames are 8 pixels wide and high, a
 whole number of every pixel block of the packet kernels (8x8 ... 1x1), so there a work unit lies wholly inside its tile or wholly

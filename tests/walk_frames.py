@@ -60,8 +60,13 @@ def make_contexts():
     return out
 
 
+# "blocks_per_cu" (a diagnostic knob, 0 = as many as fit): 1 lets the launchers see an eighth of the CUs, so that the waves of a
+# persistent kernel run many work units each on a small frame (tests/long_waves.py)
+LEVERS = {"blocks_per_cu": 0}
+
+
 def set_options(ctx, **opts):
-    for k, v in {**dc.DEFAULTS, **opts}.items():
+    for k, v in {**dc.DEFAULTS, **LEVERS, **opts}.items():
         ctx.set_option(k, v)
 
 
@@ -81,17 +86,20 @@ def frame(ctx, obj, cam, st, **opts):
         set_options(ctx)
 
 
-def planes(ctx, obj, cam, st, which):
+def planes(ctx, obj, cam, st, which, **opts):
     """the feature planes `which` of one frame: ({name: image}, kernels reported)"""
     import torch
 
-    set_options(ctx)
-    fr = mp.FrameRenderer(mp.Scene(obj), cam, st)
-    out = fr.render_aov(**{k: k in which for k in ("shade", "normal", "albedo", "ids")})
-    names = dc.launched(ctx)
-    img = {k: fr.untile_plane(out[k]).cpu().numpy() for k in which}
-    torch.cuda.synchronize()
-    return img, names
+    set_options(ctx, **opts)
+    try:
+        fr = mp.FrameRenderer(mp.Scene(obj), cam, st)
+        out = fr.render_aov(**{k: k in which for k in ("shade", "normal", "albedo", "ids")})
+        names = dc.launched(ctx)
+        img = {k: fr.untile_plane(out[k]).cpu().numpy() for k in which}
+        torch.cuda.synchronize()
+        return img, names
+    finally:
+        set_options(ctx)
 
 
 def check_formats(ctxs, make_obj, cam, st, want, name_re, **opts):
