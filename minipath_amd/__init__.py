@@ -16,9 +16,10 @@ from .temporal import TemporalAccumulator  # noqa: F401  (temporal/libminipath_t
 from .secondary import SecondaryVisibility  # noqa: F401  (secondary/libminipath_secondary.so is loaded on first use, not here)
 from .resample import GuidedResampler  # noqa: F401  (resample/libminipath_resample.so is loaded on first use, not here)
 from .lights import LocalLights  # noqa: F401  (lights/libminipath_lights.so is loaded on first use, not here)
+from .sky import SkyLight, gradient_sky  # noqa: F401  (sky/libminipath_sky.so is loaded on first use, not here)
 
 __all__ = [
     "AdaptiveSampler", "AovPlanes", "AovPlanesEx", "AtrousDenoiser", "Camera", "CameraSampler", "Context", "Instances", "FrameRenderer", "GuidedResampler", "LocalLights", "MinipathError", "MultiDeviceFrame", "ObjectGroup", "RenderProgress", "render_multi",
-    "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "SecondaryVisibility", "Sphere", "TemporalAccumulator", "TriangleBvh", "render", "render_tile",
-    "tile_ordering",
+    "RenderProgressSnapshot", "RenderSettings", "Scene", "ScreenBlock", "SecondaryVisibility", "SkyLight", "Sphere", "TemporalAccumulator", "TriangleBvh", "gradient_sky", "render",
+    "render_tile", "tile_ordering",
 ]

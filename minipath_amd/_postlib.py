@@ -1,4 +1,4 @@
-"""What the wrappers of the post-process libraries (denoise, adaptive, temporal, secondary, resample, lights) share: loading a library
+"""What the wrappers of the post-process libraries (denoise, adaptive, temporal, secondary, resample, lights, sky) share: loading a library
 of its own beside libminipath_hip.so, the buffer protocol of its mpX_last_kernels, and the checks of a device and a plane.
 torch is imported where it is used, so ``import minipath_amd`` works without it.
 """
