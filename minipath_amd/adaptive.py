@@ -8,17 +8,11 @@ libminipath_hip.so was built; there is no other compute path (a missing library 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _lib, _postlib
-from ._lib import MP_OK, MinipathError
 from .renderer import FrameRenderer
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_ADAPTIVE_SO: experiment builds of the same library; default = the in-tree build
-ADAPTIVE_SO_PATH = os.environ.get("MINIPATH_ADAPTIVE_SO") or os.path.join(_HERE, "adaptive", "libminipath_adaptive.so")
 
 # name -> (restype, argtypes); every symbol include/minipath_adaptive.h declares
 SIGNATURES = {
@@ -30,26 +24,8 @@ SIGNATURES = {
     "mpa_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib_handle = None
-
-
-def lib() -> C.CDLL:
-    """Load libminipath_adaptive.so.  Fails loudly when it has not been built."""
-    global _lib_handle
-    if _lib_handle is None:
-        _lib_handle = _postlib.load(ADAPTIVE_SO_PATH, SIGNATURES, "adaptive sampling has no CPU fallback")
-    return _lib_handle
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpa_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpa_last_kernels: the kernel of the calling thread's last launching call."""
-    return _postlib.last_kernels(lib().mpa_last_kernels, check)
+LIBRARY = _postlib.PostLibrary("adaptive", "mpa", SIGNATURES, "adaptive sampling has no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
 def round_bounds(sample_count: int, min_samples: int, round_samples: int) -> list:

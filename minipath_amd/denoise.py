@@ -7,14 +7,8 @@ only libminipath_hip.so was built; there is no other compute path (a missing lib
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 from . import _postlib
-from ._lib import MP_OK, MinipathError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_DENOISE_SO: experiment builds of the same library (kernel variants under measurement); default = the in-tree build
-DENOISE_SO_PATH = os.environ.get("MINIPATH_DENOISE_SO") or os.path.join(_HERE, "denoise", "libminipath_denoise.so")
 
 MPD_FLAG_DEMODULATE_ALBEDO = 1
 MPD_MAX_ITERATIONS = 8
@@ -37,29 +31,11 @@ SIGNATURES = {
     "mpd_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib = None
+LIBRARY = _postlib.PostLibrary("denoise", "mpd", SIGNATURES, "the denoiser has no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
-def lib() -> C.CDLL:
-    """Load libminipath_denoise.so.  Fails loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _postlib.load(DENOISE_SO_PATH, SIGNATURES, "the denoiser has no CPU fallback")
-    return _lib
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpd_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpd_last_kernels: the kernels of the calling thread's last launching call, distinct names in launch order."""
-    return _postlib.last_kernels(lib().mpd_last_kernels, check)
-
-
-class AtrousDenoiser:
+class AtrousDenoiser(_postlib.Stage):
     """The filter of include/minipath_denoise.h for one resolution (width, height) on one device; owns the scratch planes.
 
     iterations passes with tap spacing 1, 2, 4, ...; the normal weight is max(0, n_p . n_q) squared sigma_normal_pow2 times, the
@@ -79,10 +55,11 @@ class AtrousDenoiser:
         shade, shade_var = dn.denoise(fr.untile_plane(planes["shade"]), fr.untile_plane(planes["normal"]), variance=var)
     """
 
+    library, runs_on, none_passes = LIBRARY, "the denoiser runs on the GPU", True
+
     def __init__(self, resolution, device=0, iterations: int = 5, sigma_normal_pow2: int = 7, sigma_depth: float = 0.2,
                  sigma_luminance: float = 1.5, demodulate_albedo: bool = False, scratch=None):
-        self.device, self.device_id = _postlib.resolve_device(device, "the denoiser runs on the GPU")
-        self.width, self.height = int(resolution[0]), int(resolution[1])
+        super().__init__(resolution, device)
         self.settings = DenoiseSettings(C.sizeof(DenoiseSettings), self.width, self.height, int(iterations), float(sigma_normal_pow2),
                                         float(sigma_depth), float(sigma_luminance), MPD_FLAG_DEMODULATE_ALBEDO if demodulate_albedo else 0)
         if lib().mpd_scratch_floats(C.byref(self.settings), 0) == 0:
@@ -92,14 +69,6 @@ class AtrousDenoiser:
 
     def scratch_floats(self, with_variance: bool) -> int:
         return int(lib().mpd_scratch_floats(C.byref(self.settings), 1 if with_variance else 0))
-
-    def _stream(self):
-        return _postlib.stream_of(self.device)
-
-    def _plane(self, t, name):
-        if t is None:
-            return None
-        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4))
 
     def denoise(self, color, normal_depth, albedo=None, variance=None, out=None, variance_out=None):
         """mpd_atrous on the current torch stream: `out`, or (`out`, `variance_out`) when a variance plane is given.  The planes
@@ -140,7 +109,3 @@ class AtrousDenoiser:
         check(lib().mpd_variance_from_moments(self.device_id, self.width, self.height, int(sample_count), shade.data_ptr(),
                                               shade_sq.data_ptr(), out.data_ptr(), self._stream()))
         return out
-
-    def last_kernels(self) -> list:
-        """The kernels the calling thread's last launching denoiser call launched (mpd_last_kernels)."""
-        return last_kernels()

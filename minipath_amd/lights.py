@@ -8,20 +8,13 @@ it was not built; there is no other compute path (a missing library raises).
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-from . import _lib as _hip
-from . import _postlib
-from ._lib import MP_OK, MinipathError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_LIGHTS_SO: experiment builds of the same library; default = the in-tree build
-LIGHTS_SO_PATH = os.environ.get("MINIPATH_LIGHTS_SO") or os.path.join(_HERE, "lights", "libminipath_lights.so")
+from ._postlib import PostLibrary
+from ._traced import TRACED_ARRAYS, TracedStage
 
 MPL_FLAG_ACCUMULATE = 1
 MPL_MAX_LIGHTS = 8
 MPL_MAX_SAMPLES = 65536
-TRACED_ARRAYS = ("ox", "oy", "oz", "dx", "dy", "dz", "tmax")  # what mp_occluded_rays takes
 RAY_ARRAYS = TRACED_ARRAYS + ("weight",)
 
 
@@ -49,26 +42,8 @@ SIGNATURES = {
     "mpl_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib = None
-
-
-def lib() -> C.CDLL:
-    """Load libminipath_lights.so.  Fails loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _postlib.load(LIGHTS_SO_PATH, SIGNATURES, "the lights have no CPU fallback")
-    return _lib
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpl_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpl_last_kernels: the kernel of the calling thread's last launching call."""
-    return _postlib.last_kernels(lib().mpl_last_kernels, check)
+LIBRARY = PostLibrary("lights", "mpl", SIGNATURES, "the lights have no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
 def light_table(lights):
@@ -91,7 +66,7 @@ def light_table(lights):
     return table
 
 
-class LocalLights:
+class LocalLights(TracedStage):
     """Direct light of point and sphere lights (include/minipath_lights.h) for one scene and one resolution (width, height):
     shadow rays start on the surfaces the "position" and "normal" planes describe, end at the light (less `margin`), go through the
     scene's occlusion query (mp_occluded_rays) with their own tmax and come back as an irradiance plane {E.r, E.g, E.b, alpha}:
@@ -112,52 +87,21 @@ class LocalLights:
     `seed` as a SecondaryVisibility pass gives the same disc samples: offset one of them.
     """
 
+    library, runs_on = LIBRARY, "the lights run on the GPU"
+    ray_arrays, planes, max_samples = RAY_ARRAYS, ("sums", "out"), MPL_MAX_SAMPLES
+
     def __init__(self, scene, resolution, device=None, batch: int = 2):
-        obj = getattr(scene, "object", scene)
-        if obj.ctx is None:
-            raise MinipathError(1, "host-only BVH cannot be traced: pass a Context to with_obj/build")
-        if device is None:
-            device = obj.ctx.device_id
-        self.device, self.device_id = _postlib.resolve_device(device, "the lights run on the GPU")
-        if self.device_id != obj.ctx.device_id:
-            raise ValueError(f"the scene lives on device {obj.ctx.device_id}, not {self.device_id}")
-        self.scene, self.object = scene, obj
-        self.width, self.height = int(resolution[0]), int(resolution[1])
-        self.batch = int(batch)
+        super().__init__(scene, resolution, device, batch)
         one = light_table([((0.0, 0.0, 0.0), 0.0, (1.0, 1.0, 1.0))])
-        check(lib().mpl_check_settings(C.byref(self._settings(0, self.batch, 0, self.batch, 1, 0, (0, 0, 0), 0.0, 0.0)), one))
-        self._buffers, self._rays = None, 0  # made on first use
+        check(lib().mpl_check_settings(C.byref(self.batch_settings(self.batch, 0, self.batch, 1, 0, (0, 0, 0), 0.0, 0.0)), one))
 
-    @staticmethod
-    def eye_of(camera):
-        """The `eye` of a Camera: its lens centre (SecondaryVisibility.eye_of)."""
-        return [float(v) for v in camera.center_forward_up_right()[0]]
-
-    def _settings(self, flags, samples, begin, batch, light_count, seed, eye, bias, margin) -> LightsSettings:
-        st = LightsSettings(C.sizeof(LightsSettings), self.width, self.height, flags, int(samples), int(begin), int(batch), int(light_count),
-                            int(seed) & 0xFFFFFFFFFFFFFFFF)
+    def batch_settings(self, samples, begin, batch, light_count, seed, eye, bias, margin) -> LightsSettings:
+        """The mpl_settings of the batch [begin, begin + batch) of `samples` samples; it accumulates iff begin != 0."""
+        st = LightsSettings(C.sizeof(LightsSettings), self.width, self.height, MPL_FLAG_ACCUMULATE if begin else 0, int(samples), int(begin),
+                            int(batch), int(light_count), int(seed) & 0xFFFFFFFFFFFFFFFF)
         st.eye[:] = [float(v) for v in eye]
         st.bias, st.margin = float(bias), float(margin)
         return st
-
-    def _stream(self):
-        return _postlib.stream_of(self.device)
-
-    def _plane(self, t, name):
-        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4))
-
-    def _make_buffers(self, light_count: int):
-        import torch
-
-        n = self.width * self.height * self.batch * light_count
-        if self._buffers is None or self._rays < n:
-            planes = None if self._buffers is None else {k: self._buffers[k] for k in ("sums", "out")}
-            b = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k in RAY_ARRAYS}
-            b["occluded"] = torch.empty(n, dtype=torch.uint8, device=self.device)
-            for k in ("sums", "out"):
-                b[k] = planes[k] if planes else torch.empty((self.height, self.width, 4), dtype=torch.float32, device=self.device)
-            self._buffers, self._rays = b, n
-        return self._buffers
 
     def irradiance(self, position, normal, eye, lights, samples: int, seed: int = 0, bias: float = 1e-4, margin: float = 0.0):
         """(out, sums): `samples` shadow rays per hit pixel and light from position + n * bias, n the normal turned towards `eye` (a
@@ -168,27 +112,17 @@ class LocalLights:
         position, normal = self._plane(position, "position"), self._plane(normal, "normal")
         if hasattr(eye, "center_forward_up_right"):
             eye = self.eye_of(eye)
-        samples = int(samples)
-        if not 0 < samples <= MPL_MAX_SAMPLES:
-            raise ValueError(f"samples: 1 .. {MPL_MAX_SAMPLES} is expected")
+        samples = self._samples(samples)
         table = light_table(lights)
-        L = len(table)
-        b = self._make_buffers(L)
-        rays = [b[k].data_ptr() for k in RAY_ARRAYS]
-        stream = self._stream()
-        hip, ctx = _hip.lib(), self.object.ctx
-        for begin in range(0, samples, self.batch):
-            n = min(self.batch, samples - begin)
-            last = begin + n == samples
-            st = self._settings(MPL_FLAG_ACCUMULATE if begin else 0, samples, begin, n, L, seed, eye, bias, margin)
-            check(lib().mpl_generate(self.device_id, C.byref(st), table, position.data_ptr(), normal.data_ptr(), *rays, stream))
-            # the SoA buffers as they are, each ray with its own tmax; rays with tmax <= 0 are not walked
-            _hip.check(hip.mp_occluded_rays(ctx.handle, self.object.handle, *rays[:7], self.width * self.height * n * L,
-                                            b["occluded"].data_ptr(), stream))
+
+        def generate(st, b, stream):
+            check(lib().mpl_generate(self.device_id, C.byref(st), table, position.data_ptr(), normal.data_ptr(),
+                                     *[b[k].data_ptr() for k in RAY_ARRAYS], stream))
+
+        def resolve(st, b, last, stream):
             check(lib().mpl_resolve(self.device_id, C.byref(st), table, b["tmax"].data_ptr(), b["weight"].data_ptr(), b["occluded"].data_ptr(),
                                     b["sums"].data_ptr(), b["out"].data_ptr() if last else None, stream))
-        return b["out"], b["sums"]
 
-    def last_kernels(self) -> list:
-        """The kernel the calling thread's last launching call of this library launched (mpl_last_kernels)."""
-        return last_kernels()
+        b = self._trace(samples, len(table), lambda begin, n: self.batch_settings(samples, begin, n, len(table), seed, eye, bias, margin),
+                        generate, resolve)
+        return b["out"], b["sums"]

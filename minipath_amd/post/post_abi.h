@@ -1,5 +1,5 @@
-// The host side every post-process library (denoise, adaptive, temporal, secondary, resample) puts between its C ABI and its
-// kernels: the last-error and last-kernels records, the catch-all of an extern "C" body, the device scope, the launch and the
+// The host side each of the seven post-process libraries (denoise, adaptive, temporal, secondary, resample, lights, sky) puts
+// between its C ABI and its kernels: the last-error and last-kernels records, the catch-all of an extern "C" body, the device scope, the launch and the
 // overlap and alignment checks of a call's buffers.  Include it after the library's own header under include/ (the MP_* status values).
 // Everything here has internal linkage: each shared object that includes this keeps thread-local records of its own, and two
 // libraries loaded into one process share nothing.

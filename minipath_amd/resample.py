@@ -9,14 +9,8 @@ on first use, so ``import minipath_amd`` works where it was not built; there is 
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 from . import _postlib
-from ._lib import MP_OK, MinipathError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_RESAMPLE_SO: experiment builds of the same library; default = the in-tree build
-RESAMPLE_SO_PATH = os.environ.get("MINIPATH_RESAMPLE_SO") or os.path.join(_HERE, "resample", "libminipath_resample.so")
 
 MPR_PICK_PHASE, MPR_PICK_NEAREST = 0, 1
 MPR_PICK_NONE = 0xFFFFFFFF
@@ -47,26 +41,8 @@ SIGNATURES = {
     "mpr_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib = None
-
-
-def lib() -> C.CDLL:
-    """Load libminipath_resample.so.  Fails loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _postlib.load(RESAMPLE_SO_PATH, SIGNATURES, "the resampling has no CPU fallback")
-    return _lib
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpr_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpr_last_kernels: the kernel of the calling thread's last launching call."""
-    return _postlib.last_kernels(lib().mpr_last_kernels, check)
+LIBRARY = _postlib.PostLibrary("resample", "mpr", SIGNATURES, "the resampling has no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
 def pointer_array(pointers):
@@ -74,7 +50,7 @@ def pointer_array(pointers):
     return (C.c_void_p * max(len(pointers), 1))(*pointers)
 
 
-class GuidedResampler:
+class GuidedResampler(_postlib.Stage):
     """Guided resampling (include/minipath_resample.h) between one full resolution (width, height) and its f-th, f = `factor` in
     2..4: `low_resolution` = (ceil(width / f), ceil(height / f)).  Secondary visibility is traced at the low resolution, f * f times
     fewer rays, from real surface points -- one picked pixel per f x f block, never a mean across an edge -- and brought back with a
@@ -103,14 +79,15 @@ class GuidedResampler:
     and normal of the last downsample.
     """
 
+    library, runs_on = LIBRARY, "the resampling runs on the GPU"
+
     def __init__(self, resolution, factor: int = 2, device=None, sigma_normal_pow2: int = DEFAULT_SIGMA_NORMAL_POW2,
                  sigma_plane: float = DEFAULT_SIGMA_PLANE):
         import torch
 
         if device is None:
             device = torch.cuda.current_device()
-        self.device, self.device_id = _postlib.resolve_device(device, "the resampling runs on the GPU")
-        self.width, self.height = int(resolution[0]), int(resolution[1])
+        super().__init__(resolution, device)
         self.factor = int(factor)
         self.sigma_normal_pow2, self.sigma_plane = float(sigma_normal_pow2), float(sigma_plane)
         lw, lh = C.c_uint32(), C.c_uint32()
@@ -124,16 +101,12 @@ class GuidedResampler:
         return ResampleSettings(C.sizeof(ResampleSettings), self.width, self.height, self.factor, int(pick_mode), int(phase),
                                 self.sigma_normal_pow2, self.sigma_plane)
 
-    def _stream(self):
-        return _postlib.stream_of(self.device)
-
     def _plane(self, t, name, low=False, words=False):
         import torch
 
-        w, h = self.low_resolution if low else (self.width, self.height)
         # words: uint32 is taken too, the message names the two kinds callers have
         dtypes, kinds = ((torch.float32, torch.int32, torch.uint32), "float32 or int32") if words else (None, None)
-        return _postlib.expect_plane(t, name, self.device, self.device_id, (h, w, 4), dtypes, kinds)
+        return super()._plane(t, name, dtypes, kinds, self.low_resolution if low else None)
 
     def downsample(self, position, normal, *extra, phase: int = 0, pick: str = "phase"):
         """(position_lo, normal_lo, *extra_lo): the planes at each block's picked pixel, bit for bit, zeros where a block has no
@@ -180,7 +153,3 @@ class GuidedResampler:
         check(lib().mpr_upsample(self.device_id, C.byref(st), position.data_ptr(), normal.data_ptr(), self._low[0].data_ptr(),
                                  self._low[1].data_ptr(), self.picks.data_ptr(), color_lo.data_ptr(), self._out.data_ptr(), self._stream()))
         return self._out
-
-    def last_kernels(self) -> list:
-        """The kernel the calling thread's last launching call of this library launched (mpr_last_kernels)."""
-        return last_kernels()

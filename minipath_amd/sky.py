@@ -9,16 +9,10 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 
-from . import _lib as _hip
 from . import _postlib
 from . import secondary as _sec
-from ._lib import MP_OK, MinipathError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_SKY_SO: experiment builds of the same library; default = the in-tree build
-SKY_SO_PATH = os.environ.get("MINIPATH_SKY_SO") or os.path.join(_HERE, "sky", "libminipath_sky.so")
+from ._traced import TracedStage
 
 MPE_FLAG_ACCUMULATE = 1
 MPE_MAX_MAP = 8192
@@ -47,26 +41,8 @@ SIGNATURES = {
     "mpe_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib = None
-
-
-def lib() -> C.CDLL:
-    """Load libminipath_sky.so.  Fails loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _postlib.load(SKY_SO_PATH, SIGNATURES, "the sky lighting has no CPU fallback")
-    return _lib
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpe_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpe_last_kernels: the kernel of the calling thread's last launching call."""
-    return _postlib.last_kernels(lib().mpe_last_kernels, check)
+LIBRARY = _postlib.PostLibrary("sky", "mpe", SIGNATURES, "the sky lighting has no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
 def _colour(c, name):
@@ -93,7 +69,7 @@ def gradient_sky(n: int, zenith, horizon, ground, device=0):
     return env
 
 
-class SkyLight:
+class SkyLight(TracedStage):
     """Light from an environment map (include/minipath_sky.h) for one scene and one resolution (width, height): the rays of the
     ambient occlusion -- cosine-distributed about the normal, from the surfaces the "position" and "normal" planes describe -- go
     through the scene's occlusion query (mp_occluded_rays), and every ray that escapes looks its direction up in the map.  The
@@ -119,42 +95,18 @@ class SkyLight:
     The planes returned are this object's own: the next call overwrites them, so copy what has to live longer.
     """
 
+    library, runs_on = LIBRARY, "the sky lighting runs on the GPU"
+    planes, max_samples = ("sums", "out", "counts", "ao"), MPE_MAX_SAMPLES
+
     def __init__(self, scene, resolution, device=None, batch: int = 2):
-        obj = getattr(scene, "object", scene)
-        if obj.ctx is None:
-            raise MinipathError(1, "host-only BVH cannot be traced: pass a Context to with_obj/build")
-        if device is None:
-            device = obj.ctx.device_id
-        self.device, self.device_id = _postlib.resolve_device(device, "the sky lighting runs on the GPU")
-        if self.device_id != obj.ctx.device_id:
-            raise ValueError(f"the scene lives on device {obj.ctx.device_id}, not {self.device_id}")
-        self.scene, self.object = scene, obj
-        self.width, self.height = int(resolution[0]), int(resolution[1])
-        self.batch = int(batch)
-        check(lib().mpe_check_settings(C.byref(self._settings(0, self.batch, 0, self.batch, 1, 1))))
-        self._buffers = None  # made on first use
+        super().__init__(scene, resolution, device, batch)
+        check(lib().mpe_check_settings(C.byref(self.batch_settings(self.batch, 0, self.batch, 1, 1))))
 
-    @staticmethod
-    def eye_of(camera):
-        """The `eye` of a Camera: its lens centre (SecondaryVisibility.eye_of)."""
-        return [float(v) for v in camera.center_forward_up_right()[0]]
-
-    def _settings(self, flags, samples, begin, batch, map_size, pole) -> SkySettings:
-        return SkySettings(C.sizeof(SkySettings), self.width, self.height, flags, int(samples), int(begin), int(batch), int(map_size),
-                           int(pole))
-
-    def _ao_settings(self, flags, samples, begin, batch, seed, eye, radius, bias):
-        st = _sec.SecondarySettings(C.sizeof(_sec.SecondarySettings), self.width, self.height, _sec.MPS_MODE_AO, flags, int(samples),
-                                    int(begin), int(batch), int(seed) & 0xFFFFFFFFFFFFFFFF)
-        st.eye[:], st.light[:] = [float(v) for v in eye], (0.0, 0.0, 1.0)
-        st.radius, st.bias, st.spread = float(radius), float(bias), 0.0
-        return st
-
-    def _stream(self):
-        return _postlib.stream_of(self.device)
-
-    def _plane(self, t, name):
-        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4))
+    def batch_settings(self, samples, begin, batch, map_size, pole) -> SkySettings:
+        """The mpe_settings of the batch [begin, begin + batch) of `samples` samples; it accumulates iff begin != 0.  The batch's
+        rays are those of secondary.batch_settings(width, height, MPS_MODE_AO, samples, begin, batch, ...)."""
+        return SkySettings(C.sizeof(SkySettings), self.width, self.height, MPE_FLAG_ACCUMULATE if begin else 0, int(samples), int(begin),
+                           int(batch), int(map_size), int(pole))
 
     def _env(self, env):
         import torch
@@ -163,18 +115,6 @@ class SkyLight:
         if not 0 < n <= MPE_MAX_MAP:
             raise ValueError(f"env: a contiguous float32 [N, N, 4] tensor on {self.device}, 1 <= N <= {MPE_MAX_MAP}, is expected")
         return _postlib.expect_plane(env, "env", self.device, self.device_id, (n, n, 4)), n
-
-    def _make_buffers(self):
-        import torch
-
-        if self._buffers is None:
-            n = self.width * self.height * self.batch
-            b = {k: torch.empty(n, dtype=torch.float32, device=self.device) for k in RAY_ARRAYS}
-            b["occluded"] = torch.empty(n, dtype=torch.uint8, device=self.device)
-            for k in ("sums", "out", "counts", "ao"):
-                b[k] = torch.empty((self.height, self.width, 4), dtype=torch.float32, device=self.device)
-            self._buffers = b
-        return self._buffers
 
     def light(self, position, normal, camera, env, samples: int, seed: int = 0, pole: int = 1, radius: float = math.inf,
               bias: float = 1e-4, visibility: bool = False):
@@ -186,34 +126,23 @@ class SkyLight:
         position, normal = self._plane(position, "position"), self._plane(normal, "normal")
         env, n_map = self._env(env)
         eye = self.eye_of(camera) if hasattr(camera, "center_forward_up_right") else camera
-        samples = int(samples)
-        if not 0 < samples <= MPE_MAX_SAMPLES:
-            raise ValueError(f"samples: 1 .. {MPE_MAX_SAMPLES} is expected")
+        samples = self._samples(samples)
         # a bad pole is refused here, before the first batch's rays are written
-        check(lib().mpe_check_settings(C.byref(self._settings(0, samples, 0, min(self.batch, samples), n_map, pole))))
-        b = self._make_buffers()
-        rays = [b[k].data_ptr() for k in RAY_ARRAYS]
-        read = [b[k].data_ptr() for k in READ_ARRAYS]
-        stream = self._stream()
-        hip, sec, ctx = _hip.lib(), _sec.lib(), self.object.ctx
-        for begin in range(0, samples, self.batch):
-            n = min(self.batch, samples - begin)
-            last = begin + n == samples
-            st = self._settings(MPE_FLAG_ACCUMULATE if begin else 0, samples, begin, n, n_map, pole)
-            ao_st = self._ao_settings(_sec.MPS_FLAG_ACCUMULATE if begin else 0, samples, begin, n, seed, eye, radius, bias)
-            _sec.check(sec.mps_generate(self.device_id, C.byref(ao_st), position.data_ptr(), normal.data_ptr(), *rays, stream))
-            # the SoA buffers as they are: no transposes, and rays with tmax <= 0 are not walked
-            _hip.check(hip.mp_occluded_rays(ctx.handle, self.object.handle, *rays, self.width * self.height * n, b["occluded"].data_ptr(),
-                                            stream))
-            check(lib().mpe_resolve(self.device_id, C.byref(st), env.data_ptr(), *read, b["occluded"].data_ptr(), b["sums"].data_ptr(),
-                                    b["out"].data_ptr() if last else None, stream))
-            if visibility:
-                _sec.check(sec.mps_resolve(self.device_id, C.byref(ao_st), b["tmax"].data_ptr(), b["occluded"].data_ptr(),
-                                           b["counts"].data_ptr(), b["ao"].data_ptr() if last else None, stream))
+        check(lib().mpe_check_settings(C.byref(self.batch_settings(samples, 0, min(self.batch, samples), n_map, pole))))
+
+        def settings(begin, n):  # the pair: this library's, and the ambient occlusion's for the rays and the visibility
+            return (self.batch_settings(samples, begin, n, n_map, pole),
+                    _sec.batch_settings(self.width, self.height, _sec.MPS_MODE_AO, samples, begin, n, seed, eye, radius=radius, bias=bias))
+
+        def resolve(st, b, last, stream):
+            check(lib().mpe_resolve(self.device_id, C.byref(st[0]), env.data_ptr(), *[b[k].data_ptr() for k in READ_ARRAYS],
+                                    b["occluded"].data_ptr(), b["sums"].data_ptr(), b["out"].data_ptr() if last else None, stream))
+
+        def resolve_visibility(st, b, last, stream):
+            _sec.resolve(self.device_id, st[1], b, b["ao"] if last else None, stream)
+
+        b = self._trace(samples, 1, settings, lambda st, b, stream: _sec.generate(self.device_id, st[1], position, normal, b, stream),
+                        resolve, *([resolve_visibility] if visibility else []))
         if visibility:
             return b["out"], b["sums"], b["ao"], b["counts"]
         return b["out"], b["sums"]
-
-    def last_kernels(self) -> list:
-        """The kernel the calling thread's last launching call of this library launched (mpe_last_kernels)."""
-        return last_kernels()

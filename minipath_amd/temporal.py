@@ -7,16 +7,10 @@ FrameRenderer.untile / untile_plane produce them and needs no Context and no sce
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _postlib
-from ._lib import MP_OK, MinipathError
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-# MINIPATH_TEMPORAL_SO: experiment builds of the same library; default = the in-tree build
-TEMPORAL_SO_PATH = os.environ.get("MINIPATH_TEMPORAL_SO") or os.path.join(_HERE, "temporal", "libminipath_temporal.so")
 
 MPT_FLAG_MATCH_PRIM = 1
 
@@ -46,29 +40,11 @@ SIGNATURES = {
     "mpt_last_kernels": (C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
-_lib = None
+LIBRARY = _postlib.PostLibrary("temporal", "mpt", SIGNATURES, "the reprojection has no CPU fallback")
+lib, check, last_kernels = LIBRARY.load, LIBRARY.check, LIBRARY.last_kernels
 
 
-def lib() -> C.CDLL:
-    """Load libminipath_temporal.so.  Fails loudly when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = _postlib.load(TEMPORAL_SO_PATH, SIGNATURES, "the reprojection has no CPU fallback")
-    return _lib
-
-
-def check(rc: int) -> None:
-    if rc != MP_OK:
-        msg = lib().mpt_last_error()
-        raise MinipathError(rc, msg.decode() if msg else "")
-
-
-def last_kernels() -> list:
-    """mpt_last_kernels: the kernel of the calling thread's last launching call."""
-    return _postlib.last_kernels(lib().mpt_last_kernels, check)
-
-
-class TemporalAccumulator:
+class TemporalAccumulator(_postlib.Stage):
     """The temporal stage of include/minipath_temporal.h for one resolution (width, height) on one device: it owns the history
     (two ping-pong sets of colour, luminance moments, position, normal and ids), remembers the last view, and carries every pixel's
     accumulated colour over to the next frame through its world-space hit point.
@@ -96,10 +72,11 @@ class TemporalAccumulator:
     it, so copy what has to live longer.
     """
 
+    library, runs_on, none_passes = LIBRARY, "the reprojection runs on the GPU", True
+
     def __init__(self, resolution, device=0, sigma_position: float = 0.01, normal_min: float = 0.9, max_history: float = 32.0,
                  alpha_color: float = 0.2, alpha_moments: float = 0.2, min_variance_history: float = 4.0, match_prim: bool = False):
-        self.device, self.device_id = _postlib.resolve_device(device, "the reprojection runs on the GPU")
-        self.width, self.height = int(resolution[0]), int(resolution[1])
+        super().__init__(resolution, device)
         self.settings = TemporalSettings(C.sizeof(TemporalSettings), self.width, self.height, MPT_FLAG_MATCH_PRIM if match_prim else 0,
                                          float(sigma_position), float(normal_min), float(max_history), float(alpha_color),
                                          float(alpha_moments), float(min_variance_history))
@@ -120,14 +97,6 @@ class TemporalAccumulator:
         v.cx = np.float32(w - 1) * np.float32(0.5)
         v.cy = np.float32(h - 1) * np.float32(0.5)
         return v
-
-    def _stream(self):
-        return _postlib.stream_of(self.device)
-
-    def _plane(self, t, name, dtypes=None):
-        if t is None:
-            return None
-        return _postlib.expect_plane(t, name, self.device, self.device_id, (self.height, self.width, 4), dtypes)
 
     def _new_set(self):
         import torch
@@ -185,7 +154,3 @@ class TemporalAccumulator:
         if self._sets is None or self._view is None:
             raise ValueError("no frame has been accumulated")
         return self._sets[self._cur]["moments"][..., 2]
-
-    def last_kernels(self) -> list:
-        """The kernel the calling thread's last launching call of this library launched (mpt_last_kernels)."""
-        return last_kernels()

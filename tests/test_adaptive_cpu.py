@@ -219,14 +219,6 @@ def test_last_kernels_buffer_protocol():
     assert L.mpa_last_kernels(None, 4, None) == MP_ERR_INVALID
 
 
-def test_a_missing_library_raises_on_first_use_only(monkeypatch, tmp_path):
-    """import minipath_amd does not need the library; using adaptive sampling without it is an error, not a fallback"""
-    monkeypatch.setattr(ad, "_lib_handle", None)
-    monkeypatch.setattr(ad, "ADAPTIVE_SO_PATH", str(tmp_path / "libminipath_adaptive.so"))
-    with pytest.raises(ImportError):
-        ad.lib()
-
-
 def test_sampler_refuses_in_python():
     """decided from the arguments alone, before a scene, a Context or the library is touched"""
     cam = mp.Camera.teapot_view()

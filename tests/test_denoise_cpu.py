@@ -222,11 +222,3 @@ def test_last_kernels_buffer_protocol():
     need = C.c_size_t(99)
     assert L.mpd_last_kernels(None, 0, C.byref(need)) == 0 and need.value == len("\n".join(dn.last_kernels()))
     assert L.mpd_last_kernels(None, 4, None) == MP_ERR_INVALID
-
-
-def test_a_missing_library_raises_on_first_use_only(monkeypatch, tmp_path):
-    """import minipath_amd does not need the denoiser's library; using the denoiser without it is an error, not a fallback"""
-    monkeypatch.setattr(dn, "_lib", None)
-    monkeypatch.setattr(dn, "DENOISE_SO_PATH", str(tmp_path / "libminipath_denoise.so"))
-    with pytest.raises(ImportError):
-        dn.lib()

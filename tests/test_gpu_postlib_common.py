@@ -1,4 +1,4 @@
-"""GPU test of the launch path the five post-process libraries share (minipath_amd/post/post_abi.h): a call the runtime refuses
+"""GPU test of the launch path the seven post-process libraries share (minipath_amd/post/post_abi.h): a call the runtime refuses
 (hipSetDevice on a device that does not exist -- a host-side refusal, nothing is launched) must not make the library's next
 launch on the same thread report that refusal as its own.  HIP's last-error state is per thread and sticky, so launch() clears it
 before it launches.  Per library: its cheapest launching entry point on 1 x 1 planes, three times -- valid, refused device, valid
@@ -8,7 +8,7 @@ import ctypes as C
 
 import pytest
 
-from minipath_amd import adaptive, denoise, resample, secondary, temporal
+from minipath_amd import adaptive, denoise, lights, resample, secondary, sky, temporal
 
 pytestmark = pytest.mark.gpu
 
@@ -62,12 +62,29 @@ def _resample(torch):
                                                           out.data_ptr(), None)
 
 
+def _lights(torch):
+    st = lights.LightsSettings(C.sizeof(lights.LightsSettings), 1, 1, 0, 1, 0, 1, 1, 0)  # one light, one sample, in one batch
+    table = lights.light_table([((0.0, 0.0, 0.0), 0.0, (1.0, 1.0, 1.0))])
+    tmax = torch.tensor([1.0], dtype=torch.float32, device="cuda")
+    weight = torch.tensor([0.5], dtype=torch.float32, device="cuda")
+    occluded = torch.zeros(1, dtype=torch.uint8, device="cuda")
+    return lambda dev, out: lights.lib().mpl_resolve(dev, C.byref(st), table, tmax.data_ptr(), weight.data_ptr(), occluded.data_ptr(),
+                                                     out[0:4].data_ptr(), out[4:8].data_ptr(), None)
+
+
+def _sky(torch):
+    zenith, horizon, ground = ((C.c_float * 3)(*c) for c in ((0.25, 0.5, 1.0), (1.0, 0.75, 0.5), (0.125, 0.0625, 0.03125)))
+    return lambda dev, out: sky.lib().mpe_fill_gradient(dev, 1, zenith, horizon, ground, out[0:4].data_ptr(), None)
+
+
 CASES = {
     "denoise": (denoise, "mpd", "moments_kernel", _denoise),
     "adaptive": (adaptive, "mpa", "move_tiles_kernel", _adaptive),
     "temporal": (temporal, "mpt", "reset_kernel", _temporal),
     "secondary": (secondary, "mps", "resolve_kernel<true>", _secondary),
     "resample": (resample, "mpr", "downsample_kernel<0>", _resample),
+    "lights": (lights, "mpl", "irradiance_kernel<true>", _lights),
+    "sky": (sky, "mpe", "sky_gradient_kernel", _sky),
 }
 
 

@@ -4,6 +4,7 @@ conditions on the inputs of the GPU cases (tests/lights_cases.py), and what libm
 -- every refusal, the struct sizes, the symbols -- through the built library without touching a GPU."""
 import collections
 import ctypes as C
+import os
 import re
 
 import numpy as np
@@ -12,7 +13,7 @@ import pytest
 import minipath_amd as mp
 from minipath_amd import lights as ll
 from tests import lights_cases as tc, lights_model as m, secondary_model
-from tests.conftest import TEAPOT
+from tests.conftest import ROOT, TEAPOT
 from tests.lights_model import F, bits
 
 MP_ERR_INVALID, MP_ERR_HIP = 1, 4
@@ -307,7 +308,7 @@ def test_struct_sizes_and_symbols():
     assert L.mpl_settings_size() == C.sizeof(S) == 64 and C.sizeof(T) == 32
     assert [getattr(S, f).offset for f, _ in S._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32, 40, 52, 56]
     assert [getattr(T, f).offset for f, _ in T._fields_] == [0, 12, 16, 28]
-    header = open(ll.os.path.join(ll._HERE, "..", "include", "minipath_lights.h")).read()
+    header = open(os.path.join(ROOT, "include", "minipath_lights.h")).read()
     body = header.split("#ifndef MINIPATH_LIGHTS_H")[1]
     declared = set(re.findall(r"\b(mpl_[a-z_]+)\s*\(", body))
     assert declared == set(ll.SIGNATURES) and all(hasattr(L, n) for n in declared)
@@ -445,13 +446,9 @@ def test_last_kernels_buffer_protocol():
     assert L.mpl_last_kernels(buf, 1, None) == 0 and buf.raw == b"\x00xxx"  # cap 1: the terminating 0 alone
 
 
-def test_a_host_only_scene_and_a_missing_library_raise(monkeypatch, tmp_path):
-    """a scene without a Context cannot be traced (as TriangleBvh.occluded says), and without the library there is no fallback"""
+def test_a_host_only_scene_raises():
+    """a scene without a Context cannot be traced (as TriangleBvh.occluded says)"""
     host_scene = mp.Scene(mp.TriangleBvh.with_obj(TEAPOT))
     with pytest.raises(mp.MinipathError):
         mp.LocalLights(host_scene, (8, 8))
     assert mp.LocalLights.eye_of(mp.Camera.teapot_view()) == [0.0, 2.0, 10.0]
-    monkeypatch.setattr(ll, "_lib", None)
-    monkeypatch.setattr(ll, "LIGHTS_SO_PATH", str(tmp_path / "libminipath_lights.so"))
-    with pytest.raises(ImportError):
-        ll.lib()

@@ -1,5 +1,5 @@
-"""CPU tests of what the five post-process libraries share: the host scaffold of minipath_amd/post/post_abi.h, compiled into each
-library on its own, and the wrappers' helper minipath_amd/_postlib.py.  Everything here is decided before a library's first HIP
+"""CPU tests of what the seven post-process libraries share: the host scaffold of minipath_amd/post/post_abi.h, compiled into each
+library on its own, and the wrappers' helpers minipath_amd/_postlib.py and _traced.py.  Everything here is decided before a library's first HIP
 call, so the built libraries are driven without touching a GPU.
 
 A refused call leaves the record of mpX_last_kernels alone: every library's own tests assert it around each refusal they make
@@ -13,7 +13,8 @@ import ctypes as C
 import pytest
 import torch
 
-from minipath_amd import adaptive, denoise, resample, secondary, temporal
+import minipath_amd as mp
+from minipath_amd import adaptive, denoise, lights, resample, secondary, sky, temporal
 
 MP_ERR_INVALID = 1
 NO_DEVICE = 1 << 20  # no such GPU: were a call accepted by mistake, the runtime would refuse the device and nothing would be launched
@@ -36,7 +37,36 @@ LIBS = {
     "mpt": (temporal, lambda L: L.mpt_check_settings(None), b"settings is NULL"),
     "mps": (secondary, lambda L: L.mps_check_settings(None), b"settings is NULL"),
     "mpr": (resample, lambda L: L.mpr_check_settings(None), b"settings is NULL"),
+    "mpl": (lights, lambda L: L.mpl_check_settings(None, None), b"settings is NULL"),
+    "mpe": (sky, lambda L: L.mpe_check_settings(None), b"settings is NULL"),
 }
+
+
+# the wrapper module -> (how its missing library's error ends, uses of the wrapper that need the library: each raises as lib() does)
+MISSING = {
+    denoise: ("the denoiser has no CPU fallback", ()),
+    adaptive: ("adaptive sampling has no CPU fallback", ()),
+    temporal: ("the reprojection has no CPU fallback", (lambda: mp.TemporalAccumulator((8, 8), "cuda:0"),)),
+    secondary: ("the secondary rays have no CPU fallback", ()),
+    resample: ("the resampling has no CPU fallback", ()),
+    lights: ("the lights have no CPU fallback", ()),
+    sky: ("the sky lighting has no CPU fallback", (lambda: mp.gradient_sky(4, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0),)),
+}
+
+
+@pytest.mark.parametrize("mod", MISSING, ids=[m.__name__.rsplit(".", 1)[1] for m in MISSING])
+def test_a_missing_library_raises_on_first_use_only(mod, tmp_path):
+    """import minipath_amd does not need a post-process library; using one that has not been built is an error, not a fallback"""
+    what, uses = MISSING[mod]
+    name = mod.LIBRARY.name
+    with pytest.MonkeyPatch.context() as patch:
+        patch.setattr(mod.LIBRARY, "handle", None)
+        patch.setattr(mod.LIBRARY, "path", str(tmp_path / f"libminipath_{name}.so"))
+        for use in (mod.lib,) + uses:
+            with pytest.raises(ImportError) as e:
+                use()
+            assert str(e.value) == f"{tmp_path}/libminipath_{name}.so is missing: build it with `make -C minipath_amd/csrc` -- {what}"
+    assert mod.lib() is mod.LIBRARY.handle and getattr(mod.lib(), f"{mod.LIBRARY.prefix}_last_kernels")  # the real one again
 
 
 def _fn(prefix, name):
@@ -92,6 +122,8 @@ PLANE_CASES = [
     (temporal.TemporalAccumulator, {}, "ids", dict(dtypes=(torch.int32, torch.uint32)),
      "ids: a contiguous int32 or uint32 [3, 5, 4] tensor on cuda:0 is expected"),
     (secondary.SecondaryVisibility, {}, "position", {}, "position: a contiguous float32 [3, 5, 4] tensor on cuda:0 is expected"),
+    (lights.LocalLights, {}, "position", {}, "position: a contiguous float32 [3, 5, 4] tensor on cuda:0 is expected"),
+    (sky.SkyLight, {}, "position", {}, "position: a contiguous float32 [3, 5, 4] tensor on cuda:0 is expected"),
     (resample.GuidedResampler, dict(low_resolution=(3, 2)), "position", {},
      "position: a contiguous float32 [3, 5, 4] tensor on cuda:0 is expected"),
     (resample.GuidedResampler, dict(low_resolution=(3, 2)), "extra[0]", dict(words=True),
@@ -112,10 +144,12 @@ def test_plane_refusals_read_as_before(cls, attrs, name, kw, text):
 
 
 def test_none_passes_where_a_plane_is_optional():
-    """denoise and temporal hand None through (their nullable planes); secondary and resample refuse it like any non-tensor"""
+    """denoise and temporal hand None through (their nullable planes); secondary, lights, sky and resample refuse it like any
+    non-tensor"""
     assert _wrapper(denoise.AtrousDenoiser)._plane(None, "albedo") is None
     assert _wrapper(temporal.TemporalAccumulator)._plane(None, "variance") is None
-    for cls, attrs in ((secondary.SecondaryVisibility, {}), (resample.GuidedResampler, dict(low_resolution=(3, 2)))):
+    for cls, attrs in ((secondary.SecondaryVisibility, {}), (lights.LocalLights, {}), (sky.SkyLight, {}),
+                       (resample.GuidedResampler, dict(low_resolution=(3, 2)))):
         with pytest.raises(ValueError) as e:
             _wrapper(cls, **attrs)._plane(None, "position")
         assert str(e.value) == "position: a contiguous float32 [3, 5, 4] tensor on cuda:0 is expected"

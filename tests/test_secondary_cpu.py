@@ -4,6 +4,7 @@ GPU cases (tests/secondary_cases.py), and what libminipath_secondary.so decides 
 struct size, the symbols -- through the built library without touching a GPU."""
 import collections
 import ctypes as C
+import os
 import re
 
 import numpy as np
@@ -12,7 +13,7 @@ import pytest
 import minipath_amd as mp
 from minipath_amd import secondary as sv
 from tests import secondary_cases as tc, secondary_model as m
-from tests.conftest import TEAPOT
+from tests.conftest import ROOT, TEAPOT
 from tests.secondary_model import F, bits
 
 MP_ERR_INVALID, MP_ERR_HIP = 1, 4
@@ -209,7 +210,7 @@ def _settings(**kw):
 def test_struct_sizes_and_symbols():
     L = sv.lib()
     assert L.mps_settings_size() == C.sizeof(sv.SecondarySettings) == 80 and sv.SecondarySettings.spread.offset == 72
-    header = open(sv.os.path.join(sv._HERE, "..", "include", "minipath_secondary.h")).read()
+    header = open(os.path.join(ROOT, "include", "minipath_secondary.h")).read()
     declared = set(re.findall(r"\b(mps_[a-z_]+)\s*\(", header.split("#ifndef MINIPATH_SECONDARY_H")[1]))
     assert declared == set(sv.SIGNATURES) and all(hasattr(L, n) for n in declared)
     assert mp.SecondaryVisibility is sv.SecondaryVisibility and "SecondaryVisibility" in mp.__all__
@@ -315,13 +316,9 @@ def test_last_kernels_buffer_protocol():
     assert L.mps_last_kernels(buf, 1, None) == 0 and buf.raw[0] == 0  # cap 1: the terminating 0 alone
 
 
-def test_a_host_only_scene_and_a_missing_library_raise(monkeypatch, tmp_path):
-    """a scene without a Context cannot be traced (as TriangleBvh.occluded says), and without the library there is no fallback"""
+def test_a_host_only_scene_raises():
+    """a scene without a Context cannot be traced (as TriangleBvh.occluded says)"""
     host_scene = mp.Scene(mp.TriangleBvh.with_obj(TEAPOT))
     with pytest.raises(mp.MinipathError):
         mp.SecondaryVisibility(host_scene, (8, 8))
     assert mp.SecondaryVisibility.eye_of(mp.Camera.teapot_view()) == [0.0, 2.0, 10.0]
-    monkeypatch.setattr(sv, "_lib", None)
-    monkeypatch.setattr(sv, "SECONDARY_SO_PATH", str(tmp_path / "libminipath_secondary.so"))
-    with pytest.raises(ImportError):
-        sv.lib()

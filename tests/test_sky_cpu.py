@@ -4,6 +4,7 @@ compare bits against) against a float64 evaluation and against what the map stan
 through the built library without touching a GPU."""
 import collections
 import ctypes as C
+import os
 import re
 
 import numpy as np
@@ -12,7 +13,7 @@ import pytest
 import minipath_amd as mp
 from minipath_amd import sky
 from tests import secondary_model as sm, sky_cases as tc, sky_model as m, stream_cases
-from tests.conftest import TEAPOT
+from tests.conftest import ROOT, TEAPOT
 from tests.sky_model import F, bits
 
 MP_ERR_INVALID, MP_ERR_HIP = 1, 4
@@ -316,7 +317,7 @@ def test_struct_size_and_symbols():
     S = sky.SkySettings
     assert L.mpe_settings_size() == C.sizeof(S) == 36
     assert [getattr(S, f).offset for f, _ in S._fields_] == [0, 4, 8, 12, 16, 20, 24, 28, 32]
-    header = open(sky.os.path.join(sky._HERE, "..", "include", "minipath_sky.h")).read()
+    header = open(os.path.join(ROOT, "include", "minipath_sky.h")).read()
     body = header.split("#ifndef MINIPATH_SKY_H")[1]
     declared = set(re.findall(r"\b(mpe_[a-z_]+)\s*\(", body))
     assert declared == set(sky.SIGNATURES) and all(hasattr(L, n) for n in declared)
@@ -425,17 +426,11 @@ def test_last_kernels_buffer_protocol():
     assert L.mpe_last_kernels(buf, 1, None) == 0 and buf.raw == b"\x00xxx"  # cap 1: the terminating 0 alone
 
 
-def test_a_host_only_scene_and_a_missing_library_raise(monkeypatch, tmp_path):
-    """a scene without a Context cannot be traced (as TriangleBvh.occluded says), and without the library there is no fallback"""
+def test_a_host_only_scene_raises():
+    """a scene without a Context cannot be traced (as TriangleBvh.occluded says)"""
     host_scene = mp.Scene(mp.TriangleBvh.with_obj(TEAPOT))
     with pytest.raises(mp.MinipathError):
         mp.SkyLight(host_scene, (8, 8))
     assert mp.SkyLight.eye_of(mp.Camera.teapot_view()) == [0.0, 2.0, 10.0]
     with pytest.raises(ValueError):
         mp.gradient_sky(4, (1, 1, 1), (1, 1, 1), (0, 0, 0), "cpu")
-    monkeypatch.setattr(sky, "_lib", None)
-    monkeypatch.setattr(sky, "SKY_SO_PATH", str(tmp_path / "libminipath_sky.so"))
-    with pytest.raises(ImportError):
-        sky.lib()
-    with pytest.raises(ImportError):
-        mp.gradient_sky(4, (1, 1, 1), (1, 1, 1), (0, 0, 0), 0)

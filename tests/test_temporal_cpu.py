@@ -5,6 +5,7 @@ first HIP call -- every refusal, the struct size, the symbols -- through the bui
 import collections
 import ctypes as C
 import inspect
+import os
 
 import numpy as np
 import pytest
@@ -12,7 +13,7 @@ import pytest
 import minipath_amd as mp
 from minipath_amd import temporal as tp
 from tests import denoise_model, temporal_cases as tc, temporal_model as m
-from tests.conftest import TEAPOT
+from tests.conftest import ROOT, TEAPOT
 from tests.temporal_model import F, bits
 
 MP_ERR_INVALID = 1
@@ -277,7 +278,7 @@ def test_struct_sizes_and_symbols():
     L = tp.lib()
     assert L.mpt_settings_size() == C.sizeof(tp.TemporalSettings) == 40
     assert C.sizeof(tp.TemporalView) == 60
-    header = open(tp.os.path.join(tp._HERE, "..", "include", "minipath_temporal.h")).read()
+    header = open(os.path.join(ROOT, "include", "minipath_temporal.h")).read()
     import re
     declared = set(re.findall(r"\b(mpt_[a-z_]+)\s*\(", header.split("#ifndef MINIPATH_TEMPORAL_H")[1]))
     assert declared == set(tp.SIGNATURES) and all(hasattr(L, n) for n in declared)
@@ -376,13 +377,3 @@ def test_last_kernels_buffer_protocol():
     assert L.mpt_last_kernels(None, 4, None) == MP_ERR_INVALID
     buf = C.create_string_buffer(b"xxxx", 4)
     assert L.mpt_last_kernels(buf, 1, None) == 0 and buf.raw[0] == 0  # cap 1: the terminating 0 alone
-
-
-def test_a_missing_library_raises_on_first_use_only(monkeypatch, tmp_path):
-    """import minipath_amd does not need the library; using the accumulator without it is an error, not a fallback"""
-    monkeypatch.setattr(tp, "_lib", None)
-    monkeypatch.setattr(tp, "TEMPORAL_SO_PATH", str(tmp_path / "libminipath_temporal.so"))
-    with pytest.raises(ImportError):
-        tp.lib()
-    with pytest.raises(ImportError):
-        mp.TemporalAccumulator((8, 8), "cuda:0")

@@ -132,7 +132,7 @@ def bench_scene(name, bvh, cam, lamps8, margin):
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     print(f"---- {name}: {W}x{H}, hit pixels {hits:.3f}, B = {BATCH}, margin {margin}")
     lights = mp.LocalLights(scene, (W, H), batch=BATCH)
-    b = lights._make_buffers(max(COUNTS))
+    b = lights.buffers(max(COUNTS))
     rays = [b[k].data_ptr() for k in ll.RAY_ARRAYS]
     b["occluded"].random_(0, 2)  # resolve's time does not depend on the answers; something defined
     ctx = bvh.ctx
@@ -142,7 +142,7 @@ def bench_scene(name, bvh, cam, lamps8, margin):
         tables = {"spheres": ll.light_table(lamps8[:L])}
         if L == 4:
             tables["points"] = ll.light_table([(c, 0.0, it) for c, _, it in lamps8[:L]])
-        st = lights._settings(0, SAMPLES, 0, BATCH, L, 7, eye, 1e-4, margin)
+        st = lights.batch_settings(SAMPLES, 0, BATCH, L, 7, eye, 1e-4, margin)
         for tag, table in tables.items():
             def gen(st=st, table=table):
                 ll.check(ll.lib().mpl_generate(0, C.byref(st), table, position.data_ptr(), normal.data_ptr(), *rays, stream))

@@ -118,17 +118,17 @@ def bench_scene(name, bvh, cam, radius):
     bufs, runs, floors = {}, {}, {}
     for B in (4, 8):
         vis = mp.SecondaryVisibility(scene, (W, H), batch=B)
-        b = vis._make_buffers()
+        b = vis.buffers()
         bufs[B] = (vis, b)
         rays = [b[k].data_ptr() for k in sv.RAY_ARRAYS]
         for mode, tag in ((sv.MPS_MODE_AO, "ao"), (sv.MPS_MODE_SUN, "sun")):
-            st = vis._settings(mode, 0, SAMPLES, 0, B, 7, eye, light, radius if mode == sv.MPS_MODE_AO else float("inf"), 1e-4, 0.0)
+            st = sv.batch_settings(W, H, mode, SAMPLES, 0, B, 7, eye, light, radius if mode == sv.MPS_MODE_AO else float("inf"), 1e-4, 0.0)
 
             def gen(st=st, rays=rays):
                 sv.check(sv.lib().mps_generate(0, C.byref(st), position.data_ptr(), normal.data_ptr(), *rays, stream))
             runs[f"generate {tag} B={B}"] = gen
             floors[f"generate {tag} B={B}"] = pixels * (32 + 28 * B) / (COPY_GBS * 1e9) * 1e3
-        st_ao = vis._settings(sv.MPS_MODE_AO, 0, SAMPLES, 0, B, 7, eye, light, radius, 1e-4, 0.0)
+        st_ao = sv.batch_settings(W, H, sv.MPS_MODE_AO, SAMPLES, 0, B, 7, eye, light, radius, 1e-4, 0.0)
 
         def res(st=st_ao, b=b):
             sv.check(sv.lib().mps_resolve(0, C.byref(st), b["tmax"].data_ptr(), b["occluded"].data_ptr(), b["counts"].data_ptr(), b["out"].data_ptr(),
@@ -142,7 +142,7 @@ def bench_scene(name, bvh, cam, radius):
     # ---- the frame and its stages (B = 4: two batches)
     vis, b = bufs[4]
     rays = [b[k].data_ptr() for k in sv.RAY_ARRAYS]
-    st = vis._settings(sv.MPS_MODE_AO, 0, SAMPLES, 0, 4, 7, eye, light, radius, 1e-4, 0.0)
+    st = sv.batch_settings(W, H, sv.MPS_MODE_AO, SAMPLES, 0, 4, 7, eye, light, radius, 1e-4, 0.0)
     sv.check(sv.lib().mps_generate(0, C.byref(st), position.data_ptr(), normal.data_ptr(), *rays, stream))
     ctx = bvh.ctx
 

@@ -81,11 +81,11 @@ def bench_scene(name, bvh, cam, radius):
     eye = mp.SkyLight.eye_of(cam)
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     light = mp.SkyLight(scene, (W, H), batch=BATCH)
-    b = light._make_buffers()
+    b = light.buffers()
     rays = [b[k].data_ptr() for k in sky.RAY_ARRAYS]
     read = [b[k].data_ptr() for k in sky.READ_ARRAYS]
     ctx = bvh.ctx
-    ao_st = light._ao_settings(0, SAMPLES, 0, BATCH, 7, eye, radius, 1e-4)
+    ao_st = sv.batch_settings(W, H, sv.MPS_MODE_AO, SAMPLES, 0, BATCH, 7, eye, radius=radius, bias=1e-4)
 
     def generate():
         sv.check(sv.lib().mps_generate(0, C.byref(ao_st), position.data_ptr(), normal.data_ptr(), *rays, stream))
@@ -105,7 +105,7 @@ def bench_scene(name, bvh, cam, radius):
     envs = {n: mp.gradient_sky(n, device=0, **SKY) for n in MAPS}
     runs, floors = {}, {}
     for n, env in envs.items():
-        st = light._settings(0, SAMPLES, 0, BATCH, n, 1)
+        st = light.batch_settings(SAMPLES, 0, BATCH, n, 1)
 
         def res(st=st, env=env):
             sky.check(sky.lib().mpe_resolve(0, C.byref(st), env.data_ptr(), *read, b["occluded"].data_ptr(), b["sums"].data_ptr(), b["out"].data_ptr(), stream))
